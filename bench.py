@@ -18,7 +18,14 @@ touches a GPU -- starts `python -m torch.distributed.run ... bench.py <same flag
 as a child process, relays rank 0's JSON line and exits with that group's status (a failed rank
 is a failed run; nothing is retried).  Prints ONE JSON line on rank 0.
 
-The sampler-mode measurements of BASELINE configs 4 and 5 ("extras", stderr only) never share a
+A plain run sets up, warms up, times --steps steps, writes the last step's log-probabilities if
+--dump-outputs DIR is given, and prints the line: nothing else.  Everything else this file measures
+or checks runs only with --full: at N = 1 the engine clock, the fp64 FMA stream, the other
+formulations and models with their rooflines, and the CPU baseline with its parity check; at N > 1
+the strong-scaling reading (unless --scaling strong makes it the value), the per-rank parity check
+and the sampler extras.
+
+The sampler-mode measurements of BASELINE configs 4 and 5 ("extras", stderr only, --full) never share a
 process with the headline: they run in a SECOND group of ranks (`--extras-only`), started as a
 fresh child process only after the headline line is out, under a wall-clock limit (180 s), and their
 exit status is ignored -- a crash, abort or hang there cannot cost the measured line.
@@ -298,6 +305,24 @@ def rank_parity(data, taus, log_taus, bounds, theta, gpu_logp, rows=4096):
     return err, float(same_inf), n
 
 
+DUMP_ROWS = 1 << 21      # --dump-outputs: at most this many rows in all (16 MB of float64, as much again for their row numbers)
+
+
+def dump_outputs(dirname, logp, rank, world):
+    """--dump-outputs: the log-probabilities the last timed step returned, as float64 .npy files.  All rows when
+    they fit, else a fixed seeded sample (the same rows every run) with the row numbers beside it (float64, exact)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    name = 'logp' if world == 1 else f'logp_rank{rank}'
+    rows = max(1, DUMP_ROWS // world)
+    logp = np.asarray(logp, dtype=np.float64)
+    if logp.size > rows:
+        pick = np.sort(np.random.default_rng(2024 + rank).choice(logp.size, rows, replace=False))
+        np.save(os.path.join(dirname, name + '_rows.npy'), pick.astype(np.float64))
+        logp = logp[pick]
+    np.save(os.path.join(dirname, name + '.npy'), np.ascontiguousarray(logp))
+
+
 def free_port():
     s = socket.socket()
     s.bind(('127.0.0.1', 0))
@@ -412,7 +437,7 @@ def self_launch(n, args, argv):
         print(f'bench.py: expected one result line from rank 0, got {len(result)}', file=sys.stderr)
         sys.exit(1)
     print(result[0], flush=True)
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         run_extras_group(n, argv)
     sys.exit(0)
 
@@ -433,8 +458,16 @@ def main():
     ap.add_argument('--rehearse-cpu', action='store_true',
                     help='control flow only (launch, rendezvous, barriers, reductions, the JSON line) with '
                          'NO kernel: value is null.  For the CPU test of the multi-rank path; never a measurement')
+    ap.add_argument('--full', action='store_true',
+                    help='also everything beyond the headline: N = 1 the engine clock, the fp64 FMA stream, the other '
+                         'formulations and models (rooflines), the CPU baseline and its parity check; N > 1 the strong '
+                         'reading, the per-rank parity check and the cfg4 / cfg5 sampler extras')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the log-probabilities of the last one to DIR/logp.npy '
+                         '(float64; N > 1: DIR/logp_rank<r>.npy; beyond 2^21 rows a fixed seeded sample, row numbers '
+                         'in DIR/logp*_rows.npy)')
     ap.add_argument('--no-extras', '--no-sampler-extra', dest='no_extras', action='store_true',
-                    help='N > 1: skip the cfg4 / cfg5 sampler measurements that follow the result line '
+                    help='N > 1 with --full: skip the cfg4 / cfg5 sampler measurements that follow the result line '
                          '(they run in a second group of ranks, never in the processes of the headline)')
     ap.add_argument('--extras-only', action='store_true',
                     help='N > 1: ONLY the cfg4 / cfg5 sampler measurements (what the second group runs); '
@@ -442,8 +475,8 @@ def main():
     ap.add_argument('--scaling', choices=['weak', 'strong'], default='weak',
                     help="N > 1: which measurement is the line's `value`.  weak (default, the contract's per-GPU work "
                          "fixed): every rank its own --walkers rows.  strong: --walkers rows IN ALL, split into contiguous "
-                         "blocks by shard_range (SURVEY 8e) -- the north star's '>= 6x at 8 GPUs' reading.  Both are "
-                         "measured in every N > 1 run; the other one is in the line's `weak` / `strong` object.")
+                         "blocks by shard_range (SURVEY 8e) -- the north star's '>= 6x at 8 GPUs' reading.  With --full or "
+                         "--scaling strong both are measured and are in the line's `weak` / `strong` objects.")
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-variants', action='store_true')
     ap.add_argument('--pmc-pass', action='store_true',
@@ -453,6 +486,10 @@ def main():
 
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if args.dump_outputs and args.rehearse_cpu:
+        ap.error('--dump-outputs needs a kernel run: not with --rehearse-cpu')
     if args.gpus > 1 and 'RANK' not in os.environ:
         self_launch(args.gpus, args, sys.argv[1:])     # does not return
     if args.extras_only and args.gpus == 1:
@@ -559,10 +596,15 @@ def main():
                 break
             stalled_blocks.append(wall / max(args.steps, 1) * 1e3)
             wall, kern_ms = time_launches(step, args.steps, 0, torch, stream, dist)
-        # Strong scaling beside it (N > 1): the SAME W rows in all, rank r its contiguous block shard_range(W, N, r)
-        # (SURVEY 8e), timed exactly as above -- K launches between barriers, the slowest rank's clock.
+        # what the last timed step returned: written now, before anything below launches on out_t again
+        gpu_logp = out_t.cpu().numpy() if (args.dump_outputs or (args.full and world == 1)) else None
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, gpu_logp, rank, world)
+        # Strong scaling beside it (N > 1, --full or --scaling strong): the SAME W rows in all, rank r its contiguous
+        # block shard_range(W, N, r), timed exactly as above -- K launches between barriers, the slowest
+        # rank's clock.
         strong = None
-        if dist is not None and world > 1:
+        if dist is not None and world > 1 and (args.full or args.scaling == 'strong'):
             from bisip_amd.dist import shard_range
             lo_s, hi_s = shard_range(W, world, rank)
             n_s = hi_s - lo_s
@@ -575,7 +617,7 @@ def main():
 
     ranks_seen, per_rank_kernel_ms = 1, [kern_ms]
     parity = None
-    if dist is not None and world > 1 and not rehearse:
+    if dist is not None and world > 1 and not rehearse and args.full:
         # every rank checks its own shard (its own theta, seed 2024 + rank): a value summed over
         # N GPUs comes with evidence from each of them
         err, same_inf, n_chk = rank_parity(data, taus, log_taus, bounds, theta, out_t[:4096].cpu().numpy())
@@ -597,7 +639,7 @@ def main():
         wall, kern_ms = float(t[0]), float(t[1])       # slowest rank
         ranks_seen = int(round(float(one[0])))
         per_rank_kernel_ms = [float(x) for x in every.cpu()]
-        if not rehearse and world > 1:
+        if not rehearse and world > 1 and strong is not None:
             ts = torch.tensor([strong[0]], dtype=torch.float64, device=coll_dev)
             dist.all_reduce(ts, op=dist.ReduceOp.MAX)
             mine_s = torch.tensor([strong[1], float(strong[2])], dtype=torch.float64, device=coll_dev)
@@ -665,12 +707,11 @@ def main():
                 result['roofline']['counters_stale'] = True     # collected from other kernel sources: not quoted
             if parity is not None:
                 result['parity'] = parity
-            if world == 1:
+            if world == 1 and args.full:
                 result['roofline']['clock_ghz'] = engine_clock_ghz(step, kern_ms, torch)
                 counts, counts_stale = load_counters('valu_counts.json')
                 if counts_stale:
                     result['valu_counters_stale'] = True        # no roofline_valu below
-                gpu_logp = out_t.cpu().numpy()
                 if not args.no_variants:
                     fma = result['fp64_fma_stream'] = fp64_stream_ceiling(torch, stream, min(args.prime_seconds, 0.3))
                     result['variants'] = time_variants(ctx, args, step, W, torch, stream, counts, fma)
@@ -684,7 +725,7 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
-    if world > 1 and not args.no_extras and rank == 0:
+    if world > 1 and args.full and not args.no_extras and rank == 0:
         # Started by the driver's own torch.distributed.run (no parent of ours to do it): AFTER the
         # result line is out and the process group is gone, rank 0 lets go of its device memory and
         # starts the extras as a fresh child process -- `bench.py --extras-only`, which launches its

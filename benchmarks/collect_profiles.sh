@@ -26,7 +26,7 @@ step() {   # step <name> <command...>: run, log a failure, carry on
 
 if [ "$what" = bench ] || [ "$what" = all ]; then
   echo "== bench.py" | tee -a "$out/progress.log"
-  step bench python3 bench.py > "$out/bench.json" 2> "$out/bench.err"
+  step bench python3 bench.py --full > "$out/bench.json" 2> "$out/bench.err"
   echo "== bench.py under rocprofv3 --kernel-trace --stats" | tee -a "$out/progress.log"
   (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$scratch/prof_bench" -- \
       python3 "$repo/bench.py" --no-cpu-baseline --no-variants > "$out/bench_under_rocprof.json" 2> "$out/prof_bench.err") || echo "!! a rocprofv3 step failed" | tee -a "$out/progress.log"

@@ -329,7 +329,7 @@ TABLES = {
 }
 
 FILES = [
-    (rn('bench.json'), '`python bench.py`', 'the headline line: value, roofline (HIP-event kernel time), variants and other kernels with `roofline_valu`, cpu_baseline + reference calibration, parity'),
+    (rn('bench.json'), '`python bench.py --full`', 'the headline line: value, roofline (HIP-event kernel time), variants and other kernels with `roofline_valu`, cpu_baseline + reference calibration, parity'),
     (rn('bench_kernel_stats.csv'), '`rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --no-cpu-baseline --no-variants`', 'average duration of the headline kernel under the profiler'),
     (rn('bench_under_rocprof.json'), 'stdout of that run', 'the in-process HIP-event clock under the profiler (agrees with the trace)'),
     (rn('bench_pmc_summary.csv, pmc_traffic.json'), 'two more runs with `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (separate passes), `benchmarks/summarize_pmc.py`', 'HBM bytes per launch; bench.py copies it into `roofline.traffic`'),
@@ -340,7 +340,7 @@ FILES = [
     (rn('sampler_bench.jsonl, sampler_kernel_stats.csv'), '`python benchmarks/sampler_bench.py`', 'end-to-end `fit()` iterations/s per sampler / stream mode'),
     (rn('cfg4_*.json'), '`python benchmarks/cfg4_sampler.py --steps 200 --chain device [--fused] [--loop rccl|rccl-own|python]`', 'BASELINE config 4 on one GPU: fused vs the sharded half-step driven from C over RCCL vs from Python'),
     (rn('cfg5_*.json, cfg5_kernel_stats.csv'), '`python benchmarks/cfg5_batch.py --chain device --steps 500 --thin-by 40 [--no-persistent]`', "BASELINE config 5, one GPU's share (512 spectra x 256 walkers)"),
-    (rn('bench_2ranks_one_device*.json'), '`python bench.py --gpus 2 --backend gloo --same-device --walkers 1048576 --steps 4`', 'the self-launched 2-rank run on one GPU (gloo): result line and the sharded-sampler extra (state identical on both ranks = single-GPU chain)'),
+    (rn('bench_2ranks_one_device*.json'), '`python bench.py --gpus 2 --backend gloo --same-device --full --walkers 1048576 --steps 4`', 'the self-launched 2-rank run on one GPU (gloo): result line and the sharded-sampler extra (state identical on both ranks = single-GPU chain)'),
     (rn('ingest.json'), '`python benchmarks/ingest.py` (host only)', 'survey ingest: the C parser + batched arithmetic against np.loadtxt file after file, same bits'),
     (rn('batch_models.jsonl, batch_models_kernel_stats.csv'), '`python benchmarks/batch_models.py` (and `--only Polynomial` under `rocprofv3 --kernel-trace --stats`)', 'the batch-of-spectra sampler for every model at the cfg5 shape; the trace shows the stream draw next to the sampler kernel'),
     (rn('survey.jsonl'), '`python benchmarks/survey.py [--model PeltonColeCole]`', 'a 4096-spectrum survey end to end: files to posterior summaries and model bands'),

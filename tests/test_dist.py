@@ -189,7 +189,7 @@ def test_bench_starts_its_own_ranks():
     (launch, rendezvous, barriers, reductions, the one JSON line) with no kernel -- value is null.
     The extras (cfg4 / cfg5) run AFTER the line, in a second group of ranks: other processes."""
     import json
-    r = _run_bench('--gpus', '2', '--backend', 'gloo', '--rehearse-cpu', '--steps', '3', '--warmup', '1')
+    r = _run_bench('--gpus', '2', '--backend', 'gloo', '--rehearse-cpu', '--full', '--steps', '3', '--warmup', '1')
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _result_lines(r)
     assert len(lines) == 1                      # rank 0's line only; everything else went to stderr
@@ -207,7 +207,7 @@ def test_bench_headline_survives_a_crash_in_the_extras():
     """A rank of the extras group aborts (SIGABRT, as a failed assertion inside a native library
     would): the run still exits 0 with its one result line, and says what happened on stderr."""
     import json
-    r = _run_bench('--gpus', '2', '--backend', 'gloo', '--rehearse-cpu', '--steps', '2', '--warmup', '1',
+    r = _run_bench('--gpus', '2', '--backend', 'gloo', '--rehearse-cpu', '--full', '--steps', '2', '--warmup', '1',
                    env={'BISIP_BENCH_INJECT_EXTRAS_ABORT': '1'})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _result_lines(r)
@@ -224,7 +224,7 @@ def test_bench_under_the_drivers_own_launcher(crash):
     import json
     launcher = ('-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node=2', '--master-addr', '127.0.0.1',
                 '--master-port', str(_free_port()))
-    r = _run_bench('--gpus', '2', '--backend', 'gloo', '--rehearse-cpu', '--steps', '2', '--warmup', '1',
+    r = _run_bench('--gpus', '2', '--backend', 'gloo', '--rehearse-cpu', '--full', '--steps', '2', '--warmup', '1',
                    launcher=launcher, env={'BISIP_BENCH_INJECT_EXTRAS_ABORT': '1'} if crash else {'OMP_NUM_THREADS': '1'})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in _result_lines(r) if ln.startswith('{"metric"')]
@@ -236,6 +236,53 @@ def test_bench_under_the_drivers_own_launcher(crash):
         assert not extras and 'not affected' in r.stderr
     else:
         assert len(extras) == 1 and extras[0]['extras_rehearsal']['pid'] != rec['rank0_pid']
+
+
+def test_bench_plain_run_starts_no_extras():
+    """Without --full a multi-rank run is the headline alone: one line, no strong reading, no extras group."""
+    import json
+    r = _run_bench('--gpus', '2', '--backend', 'gloo', '--rehearse-cpu', '--steps', '2', '--warmup', '1')
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = _result_lines(r)
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec['n_gpus'] == 2 and rec['ranks_seen'] == 2 and rec['steps'] == 2
+    assert 'strong' not in rec and 'parity' not in rec
+    assert not [ln for ln in r.stderr.splitlines() if ln.startswith('{"extras_rehearsal"')]
+    assert 'extras group' not in r.stderr
+
+
+def test_bench_refuses_bad_step_counts_and_a_dump_without_a_kernel(tmp_path):
+    for flags in (('--steps', '0'), ('--warmup', '-1'), ('--rehearse-cpu', '--backend', 'gloo', '--dump-outputs', str(tmp_path))):
+        r = _run_bench('--gpus', '1', *flags)
+        assert r.returncode == 2 and 'error' in r.stderr, (flags, r.stderr[-2000:])
+        assert not r.stdout.strip()
+    assert not os.listdir(tmp_path)
+
+
+def test_bench_dump_outputs_writes_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float64 files; all rows when they fit, else the same seeded rows every run, never more than
+    64 MB in all, with the row numbers beside them."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert 2 * 8 * bench.DUMP_ROWS <= 64 << 20          # values and row numbers, float64
+    small = np.linspace(-5.0, 3.0, 1000)
+    small[7] = -np.inf
+    bench.dump_outputs(str(tmp_path / 'a'), small, 0, 1)
+    assert sorted(os.listdir(tmp_path / 'a')) == ['logp.npy']
+    got = np.load(tmp_path / 'a' / 'logp.npy')
+    assert got.dtype == np.float64 and np.array_equal(got, small)
+    monkeypatch.setattr(bench, 'DUMP_ROWS', 256)
+    big = np.random.default_rng(1).standard_normal(10_000)
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), big, 1, 2)
+        assert sorted(os.listdir(tmp_path / d)) == ['logp_rank1.npy', 'logp_rank1_rows.npy']
+    rows = np.load(tmp_path / 'b' / 'logp_rank1_rows.npy')
+    vals = np.load(tmp_path / 'b' / 'logp_rank1.npy')
+    assert rows.dtype == np.float64 and vals.dtype == np.float64 and rows.size == vals.size == 128
+    assert np.array_equal(rows, np.unique(rows)) and np.array_equal(vals, big[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / 'c' / 'logp_rank1_rows.npy'))
+    assert np.array_equal(vals, np.load(tmp_path / 'c' / 'logp_rank1.npy'))
 
 
 def test_bench_refuses_more_gpus_than_enumerated(tmp_path, monkeypatch):

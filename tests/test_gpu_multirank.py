@@ -75,7 +75,7 @@ def test_rccl_two_gpus_sharded_chains_equal_the_fused_chain(tmp_path):
 def test_bench_two_gpus_over_rccl():
     """`python bench.py --gpus 2`: two ranks seen, each checked against the oracle, and the extras' three
     drivers of config 4 (python / rccl-own / rccl) all equal to the single-GPU chain."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--walkers', str(1 << 22),
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--full', '--walkers', str(1 << 22),
                         '--steps', '5', '--warmup', '2'], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][0])
@@ -99,7 +99,7 @@ def test_bench_four_ranks_on_one_device():
     group of ranks) with the real kernels and more than two ranks -- four, because the pool allows six
     processes on a card and this test runner and the launcher are two of them (five ranks: the run is killed)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '4', '--backend', 'gloo',
-                        '--same-device', '--walkers', str(1 << 20), '--steps', '4', '--warmup', '1',
+                        '--same-device', '--full', '--walkers', str(1 << 20), '--steps', '4', '--warmup', '1',
                         '--prime-seconds', '0.05'], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

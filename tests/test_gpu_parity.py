@@ -1364,7 +1364,7 @@ def test_bench_two_ranks_on_one_device():
     import sys
     from conftest import ROOT
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo',
-                        '--same-device', '--walkers', str(1 << 20), '--steps', '4', '--warmup', '1',
+                        '--same-device', '--full', '--walkers', str(1 << 20), '--steps', '4', '--warmup', '1',
                         '--prime-seconds', '0.05'], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -1388,8 +1388,64 @@ def test_bench_two_ranks_on_one_device():
     assert sc['state_identical_on_every_rank'] is True and sc['equals_single_gpu_fused_chain'] is True
 
 
+def _bench_one_gpu(*flags):
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--walkers', str(1 << 20),
+                        '--steps', '3', '--warmup', '1', '--prime-seconds', '0.05', *flags],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    return json.loads(lines[0])
 
-@pytest.mark.parametrize('n_freq', [8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 19, 22, 27, 30, 32, 33, 47])
+
+def test_bench_plain_run_dumps_the_timed_outputs(tmp_path):
+    """`bench.py --gpus 1` without --full: the headline alone (no CPU baseline, other kernels or clock probe),
+    ms_per_step from exactly --steps timed steps, and --dump-outputs writes the last step's log-probabilities --
+    the same bits in a second run, and the oracle's values."""
+    import os
+    import sys
+    import oracle
+    from conftest import ROOT
+    sys.path.insert(0, ROOT)
+    import bench
+    from bisip_amd.synthetic import synthetic_theta
+    recs = [_bench_one_gpu('--dump-outputs', str(tmp_path / d)) for d in ('a', 'b')]
+    for rec in recs:
+        assert rec['metric'] == bench.METRIC and rec['unit'] == 'evals/s' and rec['dtype'] == 'f64'
+        assert rec['higher_is_better'] is True and rec['steps'] == 3 and rec['warmup'] == 1
+        assert rec['value'] == pytest.approx((1 << 20) / (rec['ms_per_step'] * 1e-3), rel=1e-9)
+        for key in ('cpu_baseline', 'parity', 'variants', 'kernels', 'fp64_fma_stream'):
+            assert key not in rec, key
+        assert 'clock_ghz' not in rec['roofline']
+    assert sorted(os.listdir(tmp_path / 'a')) == ['logp.npy']
+    a, b = (np.load(tmp_path / d / 'logp.npy') for d in ('a', 'b'))
+    assert a.dtype == np.float64 and a.shape == (1 << 20,) and np.array_equal(a, b)
+    data, taus, log_taus, bounds = bench.make_problem()
+    theta = synthetic_theta(bounds[0], bounds[1], 1 << 20, seed=2024)
+    prob = oracle.OracleProblem('PolynomialDecomposition', data['w'], data['zn'], data['zn_err'], bounds,
+                                taus=taus, log_taus=log_taus, c_exp=bench.C_EXP)
+    pick = np.arange(0, 1 << 20, 97)
+    assert_logp_close(a[pick], oracle.logprob(prob, theta[pick]))
+
+
+def test_bench_full_run_keeps_every_other_measurement():
+    """`bench.py --gpus 1 --full`: the measurements beyond the headline -- the clock probe, the FMA stream, the other
+    formulations and models, the CPU baseline and its parity check -- are in the line."""
+    rec = _bench_one_gpu('--full')
+    assert rec['value'] > 0 and rec['steps'] == 3
+    assert sorted(rec['variants']) == ['collapsed', 'faithful', 'reduced', 'reduced_comp', 'wave']
+    assert sorted(rec['kernels']) == ['colecole1', 'colecole2', 'dias2000', 'shin2015']
+    assert rec['fp64_fma_stream']['wave_instr_per_s'] > 0 and 'clock_ghz' in rec['roofline']
+    assert rec['cpu_baseline']['value'] > 0
+    assert rec['parity']['neg_inf_rows_match'] is True and rec['parity']['max_rel_err_vs_oracle'] <= 1e-10
+
+
+@pytest.mark.parametrize('n_freq',[8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 19, 22, 27, 30, 32, 33, 47])
 def test_grid_stepped_exponentials_agree_with_direct_ones_and_with_the_oracle(n_freq, monkeypatch):
     """On a geometric frequency grid (kernels.h: BOUNDS_GRID) ColeCole and Shin take one exponential per
     block of sixteen frequencies and term and step it by multiplication.  Same answer as one exponential per
