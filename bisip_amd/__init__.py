@@ -11,6 +11,7 @@ The arithmetic (prior + forward model + Gaussian log-likelihood for every walker
 runs in hand-written gfx950 kernels behind the C ABI of ``include/bisip_hip.h``.
 """
 
+from .autocorr import AutocorrError
 from .batch import SpectraBatch
 from .data import DataFiles
 from .models import (ColeCole, Dias2000, Inversion, PeltonColeCole, PolynomialDecomposition,
@@ -20,4 +21,4 @@ from .utils import load_data, load_data_batch
 
 __all__ = ('Inversion', 'PolynomialDecomposition', 'PeltonColeCole', 'ColeCole', 'Dias2000',
            'Shin2015', 'DataFiles', 'SpectraBatch', 'EnsembleSampler', 'DeviceEnsembleSampler',
-           'load_data', 'load_data_batch')
+           'load_data', 'load_data_batch', 'AutocorrError')

@@ -102,6 +102,9 @@ SYMBOLS = {
     'bisip_chain_percentiles_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                    ctypes.c_int64, ctypes.c_int, _dp, ctypes.c_int, ctypes.c_void_p,
                                                    ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    'bisip_chain_autocorr_time_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    'bisip_chain_autocorr_time_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                     ctypes.c_int64, ctypes.c_int, ctypes.c_double] + [ctypes.c_void_p] * 4),
     'bisip_column_percentiles_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     'bisip_column_percentiles_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, _dp, ctypes.c_int,
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
@@ -695,6 +698,22 @@ def chain_moments_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walker
     _check(load_library().bisip_chain_moments_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles,
                                                   walkers_per_ensemble, ndim, d_mean_ptr, d_std_ptr,
                                                   d_work_ptr, stream))
+
+
+def chain_autocorr_time_workspace(n_samples, n_ensembles, walkers_per_ensemble, ndim):
+    """Bytes of device scratch chain_autocorr_time_dev needs (0: shape not supported)."""
+    return int(load_library().bisip_chain_autocorr_time_workspace(int(n_samples), int(n_ensembles),
+                                                                  int(walkers_per_ensemble), int(ndim)))
+
+
+def chain_autocorr_time_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, c,
+                            d_tau_ptr, d_window_ptr, d_work_ptr, stream=0):
+    """emcee's integrated autocorrelation time per (ensemble, parameter) into d_tau (n_ensembles, ndim), the
+    windows into d_window (int64, or 0 / None); device pointers (ints), asynchronous on ``stream``."""
+    _check(load_library().bisip_chain_autocorr_time_dev(d_chain_ptr, int(n_samples), int(sample_stride),
+                                                        int(n_ensembles), int(walkers_per_ensemble), int(ndim),
+                                                        float(c), d_tau_ptr, d_window_ptr or None, d_work_ptr,
+                                                        stream))
 
 
 def ensemble_gram_workspace(W, ndim):

@@ -10,6 +10,7 @@ they shard as whole replicas (spectra [start, stop) per rank, no collective).
 import numpy as np
 
 from . import _hip
+from .autocorr import AutocorrError
 from .dist import shard_range
 from .sampler import DeviceEnsembleSampler
 from .utils import load_data_batch
@@ -213,6 +214,20 @@ class SpectraBatch:
             out[:, g0:g1] = res.cpu().numpy().reshape(p.size, k, cols)
             del rows, Zc, res
         return out.reshape(p.size, E, 2, N)
+
+    def get_autocorr_time(self, discard=0, thin=1, c=5, tol=50, quiet=False):
+        """emcee's integrated autocorrelation time of every parameter of every spectrum, ``(E, ndim)``, in
+        iterations of the stored chain (``thin`` times the estimate on ``get_chain(discard, thin)``), estimated on
+        the device for ``chain='device'`` and ``'host'`` alike.  Raises AutocorrError when the chain is shorter
+        than ``tol`` times an estimate (``quiet``: warns).  A multi-GPU survey joins the ranks' blocks with
+        ``gather(get_autocorr_time(...))``."""
+        if self._sampler is None:
+            raise AssertionError('Model is not fitted!')
+        try:
+            tau = self._sampler.get_autocorr_time(discard=discard, thin=thin, c=c, tol=tol, quiet=quiet)
+        except AutocorrError as err:
+            raise AutocorrError(np.reshape(err.tau, (self.n_spectra, self.ndim)), *err.args) from None
+        return np.reshape(tau, (self.n_spectra, self.ndim))
 
     def get_param_std(self, discard=0, thin=1):
         """Posterior standard deviation, ``(E, ndim)`` (src/bisip/utils.py:71-85)."""

@@ -296,6 +296,11 @@ class Inversion(_utils.utils):
         self._check_if_fitted()
         return self._sampler.get_chain(**kwargs)
 
+    def get_autocorr_time(self, **kwargs):
+        """emcee's ``sampler.get_autocorr_time``: kwargs ``discard``, ``thin``, ``c``, ``tol``, ``quiet``."""
+        self._check_if_fitted()
+        return self._sampler.get_autocorr_time(**kwargs)
+
     # -- properties (reference: src/bisip/models.py:139-179) --------------------------------
     @property
     def p0(self):

@@ -360,6 +360,13 @@ class _SamplerBase:
     def get_log_prob(self, discard=0, thin=1, flat=False):
         return self._get_value(self._log_prob, discard, thin, flat)
 
+    def get_autocorr_time(self, discard=0, thin=1, c=5, tol=50, quiet=False):
+        """emcee's estimate of the integrated autocorrelation time of every parameter,
+        ``thin * integrated_time(get_chain(discard, thin), c, tol, quiet)`` (bisip_amd.autocorr; raises
+        AutocorrError when the chain is shorter than ``tol`` times an estimate, unless ``quiet``)."""
+        from .autocorr import integrated_time
+        return thin * integrated_time(self.get_chain(discard=discard, thin=thin), c=c, tol=tol, quiet=quiet)
+
     def rows_nearest_zero_logp(self, k=256):
         """The k stored samples whose log-probability is nearest to zero, as (theta (k, ndim), logp (k,)) on
         the host: where the relative tolerance max(1, |logp|) has denominator 1 -- the rows of a run on which a
@@ -1472,6 +1479,37 @@ class DeviceEnsembleSampler(_SamplerBase):
                                mean.data_ptr(), std.data_ptr(), work.data_ptr(), be.stream())
         be.synchronize()
         return mean.cpu().numpy(), std.cpu().numpy()
+
+    def get_autocorr_time(self, discard=0, thin=1, c=5, tol=50, quiet=False):
+        """emcee's integrated autocorrelation time of ``get_chain(discard, thin)``, times ``thin``, every
+        (ensemble, parameter) estimated on the device (bisip_chain_autocorr_time_dev): from the chain where it
+        lies (``chain_on_device``), else from an upload of the used samples only.  ``(ndim,)`` for one ensemble,
+        ``(n_ensembles, ndim)`` for a batch.  The ``tol`` test is that of integrated_time, per ensemble (every
+        ensemble has the same number of samples); the AutocorrError carries every estimate."""
+        import torch
+        from .autocorr import check_c, check_tol, device_integrated_time
+        c = check_c(c)
+        discard, thin = int(discard), int(thin)
+        E, Wp, W, ndim = self.n_ensembles, self.walkers_per_ensemble, self.nwalkers, self.ndim
+        be = self.backend
+        if self.chain_on_device:
+            t = self.device_chain()
+            n_total = int(t.shape[0])
+        else:
+            n_total = self.iteration
+        first = discard + thin - 1
+        n = len(range(first, n_total, thin)) if thin >= 1 and discard >= 0 else 0
+        if n < 1:
+            raise ValueError(f'no samples left with discard={discard}, thin={thin} of {n_total} stored')
+        if self.chain_on_device:
+            tau, _ = device_integrated_time(t, n, E, Wp, ndim, c, offset=first * W * ndim,
+                                            sample_stride=thin * W * ndim, backend=be)
+        else:
+            used = torch.from_numpy(np.ascontiguousarray(self.get_chain(discard=discard, thin=thin))).to(be.device)
+            tau, _ = device_integrated_time(used, n, E, Wp, ndim, c, sample_stride=W * ndim, backend=be)
+        what = 'parameter(s)' if E == 1 else f'(ensemble, parameter) pair(s) of {E} ensembles'
+        tau = check_tol(tau if E > 1 else tau[0], n, tol, quiet, what)
+        return thin * tau
 
     def model_percentiles(self, p=(2.5, 50, 97.5), discard=0, thin=1):
         """``np.percentile(forward(get_chain(discard, thin, flat=True)), p, axis=0)`` -- the

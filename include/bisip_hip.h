@@ -41,8 +41,9 @@ extern "C" {
  * ctx_reduced_check, polydecomp_reduced_estimates, read_tables; BISIP_VARIANT_REDUCED_COMP, BISIP_ERCCL.
  * 3: clock_probe_dev, ctx_reduced_guard, polydecomp_reduced_reference, stretch_run_sharded_sim_dev (additions only).
  * 4: chain_shell_rows_dev (+ _workspace), ctx_reduced_guard_rows, ensemble_gram_dev (+ _workspace),
- *    fp64_stream_probe_dev (+ _lanes), stretch_run_philox_dev (+ stretch_philox_inline) (additions only). */
-#define BISIP_ABI_VERSION 4
+ *    fp64_stream_probe_dev (+ _lanes), stretch_run_philox_dev (+ stretch_philox_inline) (additions only).
+ * 5: chain_autocorr_time_dev (+ _workspace) (additions only). */
+#define BISIP_ABI_VERSION 5
 
 /* model_id -- the four reference model classes (src/bisip/models.py:182,232,274,308) */
 #define BISIP_MODEL_POLYDECOMP 0 /* PolynomialDecomposition -> Decomp_cyth  */
@@ -322,6 +323,24 @@ int bisip_chain_percentiles_dev(const double *d_chain, int64_t n_samples, int64_
                                 int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim,
                                 const double *percentiles, int n_percentiles, double *d_out,
                                 void *d_work, int64_t work_bytes, void *stream);
+
+/* Integrated autocorrelation time of every parameter, per ensemble, of a chain resident in device
+ * memory -- emcee's integrated_time (emcee/autocorr.py 3.1: function_1d, auto_window) with the walkers
+ * of each ensemble averaged.  Chain layout, d_chain / sample_stride conventions as for
+ * bisip_chain_moments_dev.  Every series is centred, its autocorrelation taken as direct lag sums and
+ * divided by lag 0; f = mean over the ensemble's walkers, taus = 2 cumsum(f) - 1 (sequential), and the
+ * window is the first lag k where k < c*taus_k is false (n_samples - 1 when taus_0 is NaN: a constant
+ * walker).  c: finite and > 0.  d_tau: (n_ensembles, ndim) = taus[window], in units of the samples
+ * given; d_window: (n_ensembles, ndim) int64 or NULL.  Lags go in rounds; an (ensemble, parameter)
+ * whose window is found stops there.  The tol check of integrated_time is the caller's.  d_work:
+ * bisip_chain_autocorr_time_workspace() BYTES of device memory (mean and lag 0 of every series, one
+ * round of lags per series, O(n_ensembles*ndim); 0 for a shape that is not supported).  No floating-
+ * point atomics: the same chain gives the same bits.  Asynchronous on stream. */
+int64_t bisip_chain_autocorr_time_workspace(int64_t n_samples, int64_t n_ensembles,
+                                            int64_t walkers_per_ensemble, int ndim);
+int bisip_chain_autocorr_time_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride,
+                                  int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim, double c,
+                                  double *d_tau, int64_t *d_window, void *d_work, void *stream);
 
 /* np.percentile(rows, p, axis=0) for a device-resident (n_rows, n_cols) array (linear rule):
  * d_out (n_percentiles, n_cols).  Workspace in BYTES (0: more than 2^31 values). */
