@@ -105,6 +105,11 @@ SYMBOLS = {
     'bisip_chain_autocorr_time_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
     'bisip_chain_autocorr_time_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                      ctypes.c_int64, ctypes.c_int, ctypes.c_double] + [ctypes.c_void_p] * 4),
+    'bisip_rtd_integrals_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                               ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 4),
+    'bisip_rtd_columns_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                             ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                             ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     'bisip_column_percentiles_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     'bisip_column_percentiles_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, _dp, ctypes.c_int,
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
@@ -714,6 +719,24 @@ def chain_autocorr_time_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, 
                                                         int(n_ensembles), int(walkers_per_ensemble), int(ndim),
                                                         float(c), d_tau_ptr, d_window_ptr or None, d_work_ptr,
                                                         stream))
+
+
+def rtd_integrals_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim,
+                      d_power_sums_ptr, d_norm_factor_ptr, d_out_ptr, stream=0):
+    """PolynomialDecomposition's (m_total, log_tau_mean, m_norm) of every used sample into d_out (n_samples,
+    n_ensembles * walkers_per_ensemble, 3); device pointers (ints), asynchronous on ``stream``."""
+    _check(load_library().bisip_rtd_integrals_dev(d_chain_ptr, int(n_samples), int(sample_stride), int(n_ensembles),
+                                                  int(walkers_per_ensemble), int(ndim), d_power_sums_ptr,
+                                                  d_norm_factor_ptr, d_out_ptr, stream))
+
+
+def rtd_columns_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, first_ensemble,
+                    count, d_log_tau_ptr, n_tau, d_cols_ptr, stream=0):
+    """The RTD m_l of every used sample of ensembles [first_ensemble, first_ensemble + count) into d_cols
+    (count * n_tau, n_samples * walkers_per_ensemble); device pointers (ints), asynchronous on ``stream``."""
+    _check(load_library().bisip_rtd_columns_dev(d_chain_ptr, int(n_samples), int(sample_stride), int(n_ensembles),
+                                                int(walkers_per_ensemble), int(ndim), int(first_ensemble), int(count),
+                                                d_log_tau_ptr, int(n_tau), d_cols_ptr, stream))
 
 
 def ensemble_gram_workspace(W, ndim):

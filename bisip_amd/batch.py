@@ -9,7 +9,7 @@ they shard as whole replicas (spectra [start, stop) per rank, no collective).
 
 import numpy as np
 
-from . import _hip
+from . import _hip, decomposition
 from .autocorr import AutocorrError
 from .dist import shard_range
 from .sampler import DeviceEnsembleSampler
@@ -228,6 +228,61 @@ class SpectraBatch:
         except AutocorrError as err:
             raise AutocorrError(np.reshape(err.tau, (self.n_spectra, self.ndim)), *err.args) from None
         return np.reshape(tau, (self.n_spectra, self.ndim))
+
+    # -- PolynomialDecomposition: relaxation time distribution and integrating parameters ----------------------
+    def _decomposition(self):
+        if self.model != 'PolynomialDecomposition':
+            raise ValueError(f'the RTD and its integrating parameters belong to PolynomialDecomposition, not {self.model}')
+
+    def _decomposition_sampler(self):
+        self._decomposition()
+        if self._sampler is None:
+            raise AssertionError('Model is not fitted!')
+        return self._sampler
+
+    def rtd(self, theta):
+        """The RTD ``m_l = sum_p a_p * log_tau_l**p`` of theta ``(E, n, ndim)`` on ``log_tau`` (host): ``(E, n, L)``."""
+        self._decomposition()
+        return decomposition.rtd(theta, self.log_tau)
+
+    def integrating_params(self, theta):
+        """``(m_total, log_tau_mean, m_norm)`` of theta ``(E, n, ndim)`` (host), each spectrum with its own
+        ``norm_factor``: ``(E, n, 3)``."""
+        self._decomposition()
+        theta = np.asarray(theta, dtype=np.float64)
+        if theta.ndim != 3 or theta.shape[0] != self.n_spectra:
+            raise ValueError(f'theta must have shape ({self.n_spectra}, n, {self.ndim})')
+        return decomposition.integrating_params(theta, self.log_tau, np.asarray(self.norm_factor)[:, None])
+
+    def get_integrating_chain(self, discard=0, thin=1, flat=False):
+        """``(m_total, log_tau_mean, m_norm)`` of every sample of every spectrum, computed on the GPU:
+        ``(n', E, Wp, 3)`` as get_chain, ``(E, n' * Wp, 3)`` with ``flat``."""
+        s = self._decomposition_sampler()
+        d = s.integrating_chain_dev(self.log_tau, self.norm_factor, discard=discard, thin=thin)
+        ch = d.cpu().numpy().reshape(-1, self.n_spectra, self.nwalkers, 3)
+        if flat:
+            ch = ch.transpose(1, 0, 2, 3).reshape(self.n_spectra, -1, 3)
+        return ch
+
+    def get_integrating_mean(self, discard=0, thin=1):
+        """Posterior mean of ``(m_total, log_tau_mean, m_norm)`` per spectrum, ``(E, 3)``, on the device."""
+        return self._decomposition_sampler().integrating_moments(self.log_tau, self.norm_factor, discard, thin)[0]
+
+    def get_integrating_std(self, discard=0, thin=1):
+        """Posterior standard deviation of ``(m_total, log_tau_mean, m_norm)`` per spectrum, ``(E, 3)``."""
+        return self._decomposition_sampler().integrating_moments(self.log_tau, self.norm_factor, discard, thin)[1]
+
+    def get_integrating_percentile(self, p=(2.5, 50, 97.5), discard=0, thin=1):
+        """Percentiles of ``(m_total, log_tau_mean, m_norm)`` per spectrum, ``(len(p), E, 3)`` (``(E, 3)`` for a
+        scalar ``p``).  A multi-GPU survey joins the ranks with ``gather(np.moveaxis(pct, 1, 0))``."""
+        out = self._decomposition_sampler().integrating_percentiles(p, self.log_tau, self.norm_factor, discard, thin)
+        return out if np.ndim(p) else out[0]
+
+    def get_rtd_percentile(self, p=(2.5, 50, 97.5), discard=0, thin=1):
+        """Percentiles of the RTD ``m_l`` per spectrum, ``(len(p), E, L)`` (``(E, L)`` for a scalar ``p``): the m_l
+        go column by column on the device, spectra in passes under ``decomposition.RTD_PASS_BYTES``."""
+        out = self._decomposition_sampler().rtd_percentiles(p, self.log_tau, discard, thin)
+        return out if np.ndim(p) else out[0]
 
     def get_param_std(self, discard=0, thin=1):
         """Posterior standard deviation, ``(E, ndim)`` (src/bisip/utils.py:71-85)."""

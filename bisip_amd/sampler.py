@@ -1511,6 +1511,55 @@ class DeviceEnsembleSampler(_SamplerBase):
         tau = check_tol(tau if E > 1 else tau[0], n, tol, quiet, what)
         return thin * tau
 
+    def used_samples_dev(self, discard=0, thin=1):
+        """``get_chain(discard, thin)`` on the device as ``(tensor, n, offset, sample_stride)`` (offset and stride
+        in doubles): the stored chain itself with ``chain_on_device``, else an upload of the used samples only."""
+        import torch
+        discard, thin = int(discard), int(thin)
+        W, ndim = self.nwalkers, self.ndim
+        if self.chain_on_device:
+            t = self.device_chain()
+            n_total = int(t.shape[0])
+        else:
+            n_total = self.iteration
+        first = discard + thin - 1
+        n = len(range(first, n_total, thin)) if thin >= 1 and discard >= 0 else 0
+        if n < 1:
+            raise ValueError(f'no samples left with discard={discard}, thin={thin} of {n_total} stored')
+        if self.chain_on_device:
+            return t, n, first * W * ndim, thin * W * ndim
+        used = torch.from_numpy(np.ascontiguousarray(self.get_chain(discard=discard, thin=thin))).to(self.backend.device)
+        return used, n, 0, W * ndim
+
+    def integrating_chain_dev(self, log_tau, norm_factor, discard=0, thin=1):
+        """PolynomialDecomposition's ``(m_total, log_tau_mean, m_norm)`` of every sample of ``get_chain(discard,
+        thin)`` (bisip_rtd_integrals_dev; bisip_amd.decomposition): a device tensor ``(n, nwalkers, 3)``.
+        ``norm_factor``: scalar or one per ensemble."""
+        from .decomposition import device_integrating_chain
+        t, n, offset, stride = self.used_samples_dev(discard, thin)
+        return device_integrating_chain(t, n, self.n_ensembles, self.walkers_per_ensemble, self.ndim, log_tau,
+                                        norm_factor, offset=offset, sample_stride=stride, backend=self.backend)
+
+    def integrating_moments(self, log_tau, norm_factor, discard=0, thin=1):
+        """Mean and std of the integrating parameters per ensemble, ``(n_ensembles, 3)`` each, on the device."""
+        from .decomposition import device_integrating_moments
+        d = self.integrating_chain_dev(log_tau, norm_factor, discard, thin)
+        return device_integrating_moments(d, self.n_ensembles, self.walkers_per_ensemble, backend=self.backend)
+
+    def integrating_percentiles(self, p, log_tau, norm_factor, discard=0, thin=1):
+        """np.percentile of the integrating parameters per ensemble, ``(len(p), n_ensembles, 3)``, on the device."""
+        from .decomposition import device_integrating_percentiles
+        d = self.integrating_chain_dev(log_tau, norm_factor, discard, thin)
+        return device_integrating_percentiles(d, p, self.n_ensembles, self.walkers_per_ensemble, backend=self.backend)
+
+    def rtd_percentiles(self, p, log_tau, discard=0, thin=1):
+        """np.percentile of the RTD ``m_l`` per ensemble, ``(len(p), n_ensembles, L)``, on the device
+        (bisip_rtd_columns_dev, then the selection of bisip_columns_percentiles_dev)."""
+        from .decomposition import device_rtd_percentiles
+        t, n, offset, stride = self.used_samples_dev(discard, thin)
+        return device_rtd_percentiles(t, p, n, self.n_ensembles, self.walkers_per_ensemble, self.ndim, log_tau,
+                                      offset=offset, sample_stride=stride, backend=self.backend)
+
     def model_percentiles(self, p=(2.5, 50, 97.5), discard=0, thin=1):
         """``np.percentile(forward(get_chain(discard, thin, flat=True)), p, axis=0)`` -- the
         reference's get_model_percentile (src/bisip/utils.py:17-35) -- without the chain leaving

@@ -42,8 +42,9 @@ extern "C" {
  * 3: clock_probe_dev, ctx_reduced_guard, polydecomp_reduced_reference, stretch_run_sharded_sim_dev (additions only).
  * 4: chain_shell_rows_dev (+ _workspace), ctx_reduced_guard_rows, ensemble_gram_dev (+ _workspace),
  *    fp64_stream_probe_dev (+ _lanes), stretch_run_philox_dev (+ stretch_philox_inline) (additions only).
- * 5: chain_autocorr_time_dev (+ _workspace) (additions only). */
-#define BISIP_ABI_VERSION 5
+ * 5: chain_autocorr_time_dev (+ _workspace) (additions only).
+ * 6: rtd_integrals_dev, rtd_columns_dev (additions only). */
+#define BISIP_ABI_VERSION 6
 
 /* model_id -- the four reference model classes (src/bisip/models.py:182,232,274,308) */
 #define BISIP_MODEL_POLYDECOMP 0 /* PolynomialDecomposition -> Decomp_cyth  */
@@ -341,6 +342,30 @@ int64_t bisip_chain_autocorr_time_workspace(int64_t n_samples, int64_t n_ensembl
 int bisip_chain_autocorr_time_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride,
                                   int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim, double c,
                                   double *d_tau, int64_t *d_window, void *d_work, void *stream);
+
+/* Integrating parameters of PolynomialDecomposition for every used sample of a chain resident in device
+ * memory -- what docs/tutorials/decomposition.ipynb (the get_m cell: m = sum_p a_p log_tau**p, total_m =
+ * np.sum(m)) computes by hand from the posterior mean, here per posterior sample.  theta = (r0, a_0, ..., a_P),
+ * ascending powers, ndim = P + 2 (2 ... BISIP_MAX_NDIM).  Chain layout, d_chain / sample_stride conventions
+ * as for bisip_chain_moments_dev.  d_power_sums: (ndim,) device doubles S_k = sum_l log_tau_l^k, k = 0 ... P+1,
+ * on the model's log_tau grid; d_norm_factor: (n_ensembles,) device doubles.  d_out: (n_samples,
+ * n_ensembles*walkers_per_ensemble, 3) = (m_total = sum_p a_p S_p, log_tau_mean = sum_p a_p S_{p+1} / m_total,
+ * m_norm = m_total / (r0 * norm_factor)) -- a chain of ndim = 3 that bisip_chain_moments_dev and
+ * bisip_chain_percentiles_dev summarise unchanged.  Explicit fma, IEEE division (NaN / inf where m_total is 0).
+ * Asynchronous on stream. */
+int bisip_rtd_integrals_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+                            int64_t walkers_per_ensemble, int ndim, const double *d_power_sums,
+                            const double *d_norm_factor, double *d_out, void *stream);
+
+/* The relaxation time distribution m_l = sum_p a_p log_tau_l**p of every used sample -- the curves the
+ * decomposition tutorial plots after its get_m cell (docs/tutorials/decomposition.ipynb) -- for ensembles
+ * [first_ensemble, first_ensemble + count): d_cols (count*n_tau, n_samples*walkers_per_ensemble), one column
+ * per (ensemble, l), row s*walkers_per_ensemble + w: what bisip_columns_percentiles_dev takes.  Same chain and
+ * theta conventions as bisip_rtd_integrals_dev; d_log_tau: (n_tau,) device doubles.  Horner with fma.
+ * Asynchronous on stream. */
+int bisip_rtd_columns_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+                          int64_t walkers_per_ensemble, int ndim, int64_t first_ensemble, int64_t count,
+                          const double *d_log_tau, int n_tau, double *d_cols, void *stream);
 
 /* np.percentile(rows, p, axis=0) for a device-resident (n_rows, n_cols) array (linear rule):
  * d_out (n_percentiles, n_cols).  Workspace in BYTES (0: more than 2^31 values). */
