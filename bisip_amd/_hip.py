@@ -110,6 +110,14 @@ SYMBOLS = {
     'bisip_rtd_columns_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    'bisip_chain_range_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                             ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 3),
+    'bisip_chain_histograms_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                  ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                                  ctypes.c_void_p, ctypes.c_void_p]),
+    'bisip_chain_pair_histograms_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                       ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                                       ctypes.c_void_p, ctypes.c_void_p]),
     'bisip_column_percentiles_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     'bisip_column_percentiles_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, _dp, ctypes.c_int,
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
@@ -737,6 +745,33 @@ def rtd_columns_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_
     _check(load_library().bisip_rtd_columns_dev(d_chain_ptr, int(n_samples), int(sample_stride), int(n_ensembles),
                                                 int(walkers_per_ensemble), int(ndim), int(first_ensemble), int(count),
                                                 d_log_tau_ptr, int(n_tau), d_cols_ptr, stream))
+
+
+def chain_range_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, d_out_ptr,
+                    d_nonfinite_ptr, stream=0):
+    """Min and max of the finite values per (ensemble, parameter) into d_out (n_ensembles, ndim, 2), the number of
+    non-finite values into d_nonfinite (n_ensembles, ndim) int64; device pointers (ints), asynchronous on ``stream``."""
+    _check(load_library().bisip_chain_range_dev(d_chain_ptr, int(n_samples), int(sample_stride), int(n_ensembles),
+                                                int(walkers_per_ensemble), int(ndim), d_out_ptr, d_nonfinite_ptr,
+                                                stream))
+
+
+def chain_histograms_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, d_edges_ptr,
+                         bins, d_counts_ptr, stream=0):
+    """np.histogram's counts of every (ensemble, parameter) within d_edges (n_ensembles, ndim, bins + 1) into d_counts
+    (n_ensembles, ndim, bins) int64; device pointers (ints), asynchronous on ``stream``."""
+    _check(load_library().bisip_chain_histograms_dev(d_chain_ptr, int(n_samples), int(sample_stride), int(n_ensembles),
+                                                     int(walkers_per_ensemble), int(ndim), d_edges_ptr, int(bins),
+                                                     d_counts_ptr, stream))
+
+
+def chain_pair_histograms_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim,
+                              d_edges_ptr, bins, d_counts_ptr, stream=0):
+    """np.histogram2d's counts of every pair of parameters (np.triu_indices(ndim, 1) order) within d_edges into
+    d_counts (n_ensembles, ndim (ndim - 1) / 2, bins, bins) int64; device pointers (ints), asynchronous on ``stream``."""
+    _check(load_library().bisip_chain_pair_histograms_dev(d_chain_ptr, int(n_samples), int(sample_stride),
+                                                          int(n_ensembles), int(walkers_per_ensemble), int(ndim),
+                                                          d_edges_ptr, int(bins), d_counts_ptr, stream))
 
 
 def ensemble_gram_workspace(W, ndim):

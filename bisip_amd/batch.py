@@ -229,6 +229,27 @@ class SpectraBatch:
             raise AutocorrError(np.reshape(err.tau, (self.n_spectra, self.ndim)), *err.args) from None
         return np.reshape(tau, (self.n_spectra, self.ndim))
 
+    def _histogram_sampler(self):
+        if self._sampler is None:
+            raise AssertionError('Model is not fitted!')
+        return self._sampler
+
+    def get_param_histogram(self, bins=25, range=None, discard=0, thin=1):
+        """``np.histogram`` of every parameter of every spectrum, ``(counts (E, ndim, bins) int64, edges (E, ndim,
+        bins + 1))`` -- per spectrum the counts of the reference's plot_histograms (src/bisip/plotlib.py:56-90) --
+        counted on the device for ``chain='device'`` and ``'host'`` alike.  ``range``: None (each spectrum's own min
+        and max), 'bounds' (the prior box: the same edges for every spectrum) or an array ``(ndim, 2)`` / ``(E, ndim,
+        2)``."""
+        return self._histogram_sampler().param_histograms(bins, range, discard=discard, thin=thin,
+                                                          bounds=self.param_bounds)
+
+    def get_corner_histograms(self, bins=20, range=None, discard=0, thin=1):
+        """``np.histogram2d`` of every pair of parameters of every spectrum, ``(counts (E, npairs, bins, bins) int64,
+        edges (E, ndim, bins + 1), pairs)`` with ``pairs = np.triu_indices(ndim, 1)`` -- per spectrum the panels of
+        the reference's plot_corner (src/bisip/plotlib.py:233-259)."""
+        return self._histogram_sampler().pair_histograms(bins, range, discard=discard, thin=thin,
+                                                         bounds=self.param_bounds)
+
     # -- PolynomialDecomposition: relaxation time distribution and integrating parameters ----------------------
     def _decomposition(self):
         if self.model != 'PolynomialDecomposition':

@@ -19,6 +19,7 @@ import numpy as np
 from . import _hip
 from . import decomposition as _decomp
 from . import utils as _utils
+from .plotlib import plotlib as _plotlib
 from .sampler import DeviceEnsembleSampler, EnsembleSampler
 
 
@@ -27,7 +28,7 @@ def moves_sampler(sampler):
     return not isinstance(sampler, (DeviceEnsembleSampler, EnsembleSampler))
 
 
-class Inversion(_utils.utils):
+class Inversion(_plotlib, _utils.utils):
     """Base class for the SIP inversion models (reference: src/bisip/models.py:21-179).
 
     Args:

@@ -1531,6 +1531,53 @@ class DeviceEnsembleSampler(_SamplerBase):
         used = torch.from_numpy(np.ascontiguousarray(self.get_chain(discard=discard, thin=thin))).to(self.backend.device)
         return used, n, 0, W * ndim
 
+    def param_range(self, discard=0, thin=1):
+        """Min and max of the finite values of every parameter over ``get_chain(discard, thin)`` per ensemble,
+        ``(n_ensembles, ndim, 2)``, and how many of its values are not finite, ``(n_ensembles, ndim)``, taken on the
+        device (bisip_chain_range_dev)."""
+        from .histogram import device_param_range
+        t, n, offset, stride = self.used_samples_dev(discard, thin)
+        return device_param_range(t, n, self.n_ensembles, self.walkers_per_ensemble, self.ndim, offset=offset,
+                                  sample_stride=stride, backend=self.backend)
+
+    def _histogram_edges(self, bins, range, discard, thin, bounds):
+        """The used samples on the device and the edges ``(n_ensembles, ndim, bins + 1)`` of a ``range`` argument
+        (None, 'bounds' or an array: bisip_amd.histogram)."""
+        from . import histogram as hg
+        bins = hg.check_bins(bins)
+        E, Wp, ndim = self.n_ensembles, self.walkers_per_ensemble, self.ndim
+        used = self.used_samples_dev(discard, thin)
+        t, n, offset, stride = used
+
+        def data_range():
+            return hg.device_param_range(t, n, E, Wp, ndim, offset=offset, sample_stride=stride, backend=self.backend)
+        return used, hg.edges_from_range(hg.resolve_range(range, E, ndim, bounds, data_range), bins)
+
+    def param_histograms(self, bins=25, range=None, discard=0, thin=1, bounds=None):
+        """``np.histogram`` of every parameter of every ensemble over ``get_chain(discard, thin, flat=True)`` -- the
+        counts of the reference's plot_histograms (src/bisip/plotlib.py:56-90) -- counted on the device
+        (bisip_chain_histograms_dev): from the chain where it lies (``chain_on_device``), else from an upload of the
+        used samples only.  ``range``: None (min and max of the samples), 'bounds' (the prior box ``bounds (2, ndim)``)
+        or an array ``(ndim, 2)`` / ``(n_ensembles, ndim, 2)``.  Returns ``(counts (n_ensembles, ndim, bins) int64, edges
+        (n_ensembles, ndim, bins + 1))``."""
+        from .histogram import device_histograms
+        (t, n, offset, stride), edges = self._histogram_edges(bins, range, discard, thin, bounds)
+        counts = device_histograms(t, edges, n, self.n_ensembles, self.walkers_per_ensemble, self.ndim, offset=offset,
+                                   sample_stride=stride, backend=self.backend)
+        return counts, edges
+
+    def pair_histograms(self, bins=20, range=None, discard=0, thin=1, bounds=None):
+        """``np.histogram2d`` of every pair of parameters of every ensemble -- the panels of the reference's
+        plot_corner (src/bisip/plotlib.py:233-259) -- counted on the device (bisip_chain_pair_histograms_dev).
+        Returns ``(counts (n_ensembles, npairs, bins, bins) int64, edges (n_ensembles, ndim, bins + 1), pairs)``,
+        ``pairs = np.triu_indices(ndim, 1)``; ``counts[e, q, a, b]``: parameter ``pairs[0][q]`` in bin ``a``,
+        ``pairs[1][q]`` in bin ``b``."""
+        from .histogram import device_pair_histograms, pair_index
+        (t, n, offset, stride), edges = self._histogram_edges(bins, range, discard, thin, bounds)
+        counts = device_pair_histograms(t, edges, n, self.n_ensembles, self.walkers_per_ensemble, self.ndim,
+                                        offset=offset, sample_stride=stride, backend=self.backend)
+        return counts, edges, pair_index(self.ndim)
+
     def integrating_chain_dev(self, log_tau, norm_factor, discard=0, thin=1):
         """PolynomialDecomposition's ``(m_total, log_tau_mean, m_norm)`` of every sample of ``get_chain(discard,
         thin)`` (bisip_rtd_integrals_dev; bisip_amd.decomposition): a device tensor ``(n, nwalkers, 3)``.

@@ -193,11 +193,12 @@ class utils(object):
         out = self._context().forward_percentiles(chain, p)
         return out if np.ndim(p) else out[0]
 
-    def _device_chain_sampler(self, chain, kwargs):
+    def _device_chain_sampler(self, chain, kwargs, having='chain_on_device'):
         """The sampler, when its chain lives in HBM (fit(chain='device')) and the caller asked for a
-        summary of the fitted chain rather than of an array of its own; else None."""
+        summary of the fitted chain rather than of an array of its own; else None.  ``having``: what the
+        sampler must have instead (a method of the device sampler that also takes a host chain)."""
         s = getattr(self, '_sampler', None)
-        if chain is not None or not getattr(s, 'chain_on_device', False):
+        if chain is not None or not getattr(s, having, False):
             return None
         self._check_if_fitted()
         extra = set(kwargs) - {'discard', 'thin', 'flat'}
@@ -230,6 +231,36 @@ class utils(object):
         if s is not None:
             return s.param_moments(discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1))[1][0]
         return np.std(self.parse_chain(chain, **kwargs), axis=0)
+
+    def get_param_histogram(self, bins=25, range=None, chain=None, **kwargs):
+        """``np.histogram(chain[:, i], bins, range[i])`` of every parameter -- the counts of the reference's
+        plot_histograms (src/bisip/plotlib.py:56-90): ``(counts (ndim, bins) int64, edges (ndim, bins + 1))``.
+        ``range``: None (min and max of the samples), 'bounds' (``param_bounds``) or an array ``(ndim, 2)``.
+        ``chain`` / ``discard`` / ``thin`` as parse_chain; a fit with the device sampler is counted on the GPU
+        (``chain='device'``: where the chain lies), an explicit ``chain`` or a host sampler's in NumPy
+        (bisip_amd.histogram): the same integers."""
+        from . import histogram as hg
+        bins = hg.check_bins(bins)
+        s = self._device_chain_sampler(chain, kwargs, 'param_histograms')
+        if s is not None:      # the device sampler: counted on the GPU, a host chain by upload of the used samples
+            counts, edges = s.param_histograms(bins, range, discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1),
+                                               bounds=self.param_bounds)
+            return counts[0], edges[0]
+        return hg.host_histograms(self.parse_chain(chain, **kwargs), bins, range, self.param_bounds)
+
+    def get_corner_histograms(self, bins=20, range=None, chain=None, **kwargs):
+        """``np.histogram2d`` of every pair of parameters -- the panels of the reference's plot_corner
+        (src/bisip/plotlib.py:233-259): ``(counts (npairs, bins, bins) int64, edges (ndim, bins + 1), pairs)`` with
+        ``pairs = np.triu_indices(ndim, 1)`` and ``counts[q, a, b]`` the samples with parameter ``pairs[0][q]`` in bin
+        ``a`` and ``pairs[1][q]`` in bin ``b``.  Arguments as get_param_histogram."""
+        from . import histogram as hg
+        bins = hg.check_bins(bins)
+        s = self._device_chain_sampler(chain, kwargs, 'pair_histograms')
+        if s is not None:
+            counts, edges, pairs = s.pair_histograms(bins, range, discard=kwargs.get('discard', 0),
+                                                     thin=kwargs.get('thin', 1), bounds=self.param_bounds)
+            return counts[0], edges[0], pairs
+        return hg.host_pair_histograms(self.parse_chain(chain, **kwargs), bins, range, self.param_bounds)
 
 
 _QUOTA_APPLIED = False

@@ -43,7 +43,8 @@ extern "C" {
  * 4: chain_shell_rows_dev (+ _workspace), ctx_reduced_guard_rows, ensemble_gram_dev (+ _workspace),
  *    fp64_stream_probe_dev (+ _lanes), stretch_run_philox_dev (+ stretch_philox_inline) (additions only).
  * 5: chain_autocorr_time_dev (+ _workspace) (additions only).
- * 6: rtd_integrals_dev, rtd_columns_dev (additions only). */
+ * 6: rtd_integrals_dev, rtd_columns_dev (additions only); chain_range_dev, chain_histograms_dev,
+ *    chain_pair_histograms_dev came later under the same number (additions only). */
 #define BISIP_ABI_VERSION 6
 
 /* model_id -- the four reference model classes (src/bisip/models.py:182,232,274,308) */
@@ -366,6 +367,33 @@ int bisip_rtd_integrals_dev(const double *d_chain, int64_t n_samples, int64_t sa
 int bisip_rtd_columns_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
                           int64_t walkers_per_ensemble, int ndim, int64_t first_ensemble, int64_t count,
                           const double *d_log_tau, int n_tau, double *d_cols, void *stream);
+
+/* The shapes of the posterior of a chain resident in device memory: the counts the reference draws in
+ * plot_histograms (src/bisip/plotlib.py:56-90: np.histogram of every parameter, bins = 25) and in plot_corner
+ * (src/bisip/plotlib.py:233-259: corner's 1-D and pairwise 2-D histograms, bins = 20).  Chain layout, d_chain /
+ * sample_stride conventions as for bisip_chain_moments_dev; ndim 1 ... BISIP_MAX_NDIM (pairs: from 2).
+ * Bin edges are made on the host (np.linspace) and uploaded: d_edges (n_ensembles, ndim, bins + 1) doubles, ascending.
+ * Value x is in bin i iff edges[i] <= x < edges[i+1]; x == edges[bins] is in the last bin; anything else (outside the
+ * edges, NaN) is counted nowhere -- the integers of np.histogram / np.histogram2d with the same edges.
+ *   bisip_chain_range_dev: d_out (n_ensembles, ndim, 2) = min and max of the FINITE values of every (ensemble,
+ *     parameter) ((+inf, -inf) when there is none); d_nonfinite (n_ensembles, ndim) int64 = how many values are NaN
+ *     or +-inf (np.histogram's range=None refuses those).
+ *   bisip_chain_histograms_dev: d_counts (n_ensembles, ndim, bins) int64, all parameters in one pass over the chain.
+ *   bisip_chain_pair_histograms_dev: d_counts (n_ensembles, ndim (ndim - 1) / 2, bins, bins) int64, pairs (j, k), j < k,
+ *     in np.triu_indices(ndim, 1) order; counts[e, q, a, b] = rows with parameter j_q in bin a and k_q in bin b; a row
+ *     outside the edges in either coordinate is left out of that pair only.  Pairs whose counters do not fit the
+ *     LDS of one workgroup together go in groups (one more read of the chain per group).
+ * LDS counters, integer atomics only: the same chain gives the same integers.  No workspace; BISIP_EUNSUPPORTED
+ * when the edges and counters of the parameters (1-D) or of a single pair (2-D: bins up to ~125) exceed 64 KiB of LDS.
+ * Any number of values per call (64-bit offsets).  Asynchronous on stream, no host synchronisation. */
+int bisip_chain_range_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+                          int64_t walkers_per_ensemble, int ndim, double *d_out, int64_t *d_nonfinite, void *stream);
+int bisip_chain_histograms_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+                               int64_t walkers_per_ensemble, int ndim, const double *d_edges, int bins,
+                               int64_t *d_counts, void *stream);
+int bisip_chain_pair_histograms_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride,
+                                    int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim, const double *d_edges,
+                                    int bins, int64_t *d_counts, void *stream);
 
 /* np.percentile(rows, p, axis=0) for a device-resident (n_rows, n_cols) array (linear rule):
  * d_out (n_percentiles, n_cols).  Workspace in BYTES (0: more than 2^31 values). */
