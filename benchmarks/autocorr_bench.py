@@ -198,10 +198,12 @@ def main():
     if args.child:                   # under rocprofv3: the calls only
         E, Wp, ndim, stored, discard = SHAPES[args.child]
         from bisip_amd.autocorr import device_integrated_time
+        from bisip_amd.chainview import ChainView
         x = make_chain(E, Wp, ndim, stored)
         W, n = E * Wp, stored - discard
+        view = ChainView(x, n, E, Wp, ndim, offset=discard * W * ndim, stride=W * ndim)
         for _ in range(args.reps + 2):
-            device_integrated_time(x, n, E, Wp, ndim, 5.0, offset=discard * W * ndim, sample_stride=W * ndim)
+            device_integrated_time(view, 5.0)
         return
     import tempfile
     with tempfile.TemporaryDirectory(prefix='autocorr_bench_') as tmp:

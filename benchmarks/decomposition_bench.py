@@ -54,21 +54,24 @@ def norm_factors(E):
 
 def device_calls(x, E, Wp, P, n, discard):
     from bisip_amd import decomposition as dc
+    from bisip_amd.chainview import ChainView, device_moments, device_percentiles
     W, ndim = E * Wp, P + 2
     nf = norm_factors(E)
 
+    def view():
+        return ChainView(x, n, E, Wp, ndim, offset=discard * W * ndim, stride=W * ndim)
+
     def derived():
-        return dc.device_integrating_chain(x, n, E, Wp, ndim, LOG_TAU, nf, offset=discard * W * ndim,
-                                           sample_stride=W * ndim)
+        v = view()
+        return v.derived(dc.device_integrating_chain(v, LOG_TAU, nf))
 
     def integrating():           # get_integrating_mean, get_integrating_std, get_integrating_percentile
-        dc.device_integrating_moments(derived(), E, Wp)
-        dc.device_integrating_moments(derived(), E, Wp)
-        dc.device_integrating_percentiles(derived(), P_BAND, E, Wp)
+        device_moments(derived())
+        device_moments(derived())
+        device_percentiles(derived(), P_BAND)
 
     def band():
-        dc.device_rtd_percentiles(x, P_BAND, n, E, Wp, ndim, LOG_TAU, offset=discard * W * ndim,
-                                  sample_stride=W * ndim)
+        dc.device_rtd_percentiles(view(), P_BAND, LOG_TAU)
     return integrating, band
 
 

@@ -102,10 +102,10 @@ def integrated_time(x, c=5, tol=50, quiet=False, has_walkers=True):
     warns and returns).  A float64 torch tensor on the GPU is estimated there."""
     c = check_c(c)
     if _is_device_tensor(x):
-        x = _as_3d(x, has_walkers)
-        n_t, n_w, n_d = (int(v) for v in x.shape)
-        tau, _ = device_integrated_time(x, n_t, 1, n_w, n_d, c)
-        return check_tol(tau[0], n_t, tol, quiet)
+        from .chainview import ChainView
+        view = ChainView.of_tensor(_as_3d(x, has_walkers))
+        tau, _ = device_integrated_time(view, c)
+        return check_tol(tau[0], view.n, tol, quiet)
     x = _as_3d(np.atleast_1d(np.asarray(x)), has_walkers)
     n_t, n_w, n_d = x.shape
     tau_est = np.empty(n_d)
@@ -116,38 +116,20 @@ def integrated_time(x, c=5, tol=50, quiet=False, has_walkers=True):
     return check_tol(tau_est, n_t, tol, quiet)
 
 
-def device_integrated_time(chain, n_samples, n_ensembles, walkers_per_ensemble, ndim, c, offset=0, sample_stride=None,
-                           backend=None):
-    """tau and windows ``(n_ensembles, ndim)`` (NumPy) of samples ``offset``, ``offset + sample_stride``, ... of a
-    float64 device tensor ``chain`` whose samples hold ``(n_ensembles * walkers_per_ensemble, ndim)`` rows (strides
-    in doubles).  No tol check.  ``backend``: a HipStretchBackend (its stream and allocator), else torch's."""
+def device_integrated_time(view, c):
+    """tau and windows ``(n_ensembles, ndim)`` (NumPy) of the samples of a ChainView (bisip_amd.chainview).  No tol
+    check."""
     import torch
     from . import _hip
     c = check_c(c)
-    if chain.dtype != torch.float64:
-        raise TypeError('the chain must be float64')
-    row = n_ensembles * walkers_per_ensemble * ndim
-    if sample_stride is None:
-        if tuple(chain.stride()[-2:]) != (ndim, 1) or chain.shape[-2] * ndim != row or (
-                n_samples > 1 and chain.stride(0) < row):
-            chain = chain.contiguous()
-        sample_stride = chain.stride(0) if n_samples > 1 else row
-    nbytes = _hip.chain_autocorr_time_workspace(n_samples, n_ensembles, walkers_per_ensemble, ndim)
+    n, E, Wp, ndim = view.n, view.n_ensembles, view.walkers_per_ensemble, view.ndim
+    nbytes = _hip.chain_autocorr_time_workspace(n, E, Wp, ndim)
     if nbytes <= 0:
-        raise ValueError(f'chain shape ({n_samples}, {n_ensembles} x {walkers_per_ensemble}, {ndim}) not supported')
-    if backend is not None:
-        empty, stream, sync = backend.empty, backend.stream(), backend.synchronize
-    else:
-        dev = chain.device
-
-        def empty(shape, dtype):
-            return torch.empty(shape, dtype=dtype, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        sync = torch.cuda.current_stream(dev).synchronize
-    work = empty((nbytes,), torch.uint8)
-    tau = empty((n_ensembles, ndim), torch.float64)
-    win = empty((n_ensembles, ndim), torch.int64)
-    _hip.chain_autocorr_time_dev(chain.data_ptr() + 8 * int(offset), n_samples, sample_stride, n_ensembles,
-                                 walkers_per_ensemble, ndim, c, tau.data_ptr(), win.data_ptr(), work.data_ptr(), stream)
-    sync()
+        raise ValueError(f'chain shape ({n}, {E} x {Wp}, {ndim}) not supported')
+    work = view.empty((nbytes,), torch.uint8)
+    tau = view.empty((E, ndim), torch.float64)
+    win = view.empty((E, ndim), torch.int64)
+    _hip.chain_autocorr_time_dev(view.ptr, n, view.stride, E, Wp, ndim, c, tau.data_ptr(), win.data_ptr(),
+                                 work.data_ptr(), view.stream)
+    view.synchronize()
     return tau.cpu().numpy(), win.cpu().numpy()

@@ -182,26 +182,17 @@ class SpectraBatch:
         import torch
         if self._sampler is None:
             raise AssertionError('Model is not fitted!')
-        s = self._sampler
-        be = s.backend
+        be = self._sampler.backend
         E, Wp, ndim, N = self.n_spectra, self.nwalkers, self.ndim, self.N
         p = np.atleast_1d(np.asarray(p, dtype=np.float64))
-        discard, thin = int(discard), int(thin)
-        if s.chain_on_device:
-            t = s.device_chain()
-        else:
-            t = torch.from_numpy(s.get_chain()).to(be.device)
-        first = discard + thin - 1
-        used = t[first::thin] if thin >= 1 else t[:0]
-        n = int(used.shape[0])
-        if thin < 1 or discard < 0 or n < 1:
-            raise ValueError(f'no samples left with discard={discard}, thin={thin} of {int(t.shape[0])} stored')
+        view = self._sampler.used_samples_dev(discard, thin)
+        n = view.n
         rows_per = n * Wp
         cols = 2 * N
-        # spectra per pass: the responses of a pass stay under ~8 GB
-        G = int(min(E, max(1, (8 << 30) // (rows_per * cols * 8))))
+        # spectra per pass: the responses of a pass stay under decomposition.RTD_PASS_BYTES
+        G = int(min(E, max(1, decomposition.RTD_PASS_BYTES // (rows_per * cols * 8))))
         out = np.empty((p.size, E, cols))
-        grid = used.reshape(n, E, Wp, ndim)
+        grid = view.samples().reshape(n, E, Wp, ndim)
         for g0 in range(0, E, G):
             g1 = min(E, g0 + G)
             k = g1 - g0

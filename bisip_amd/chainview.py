@@ -1,0 +1,131 @@
+"""The used samples of a chain on the device, as every posterior summary takes them.
+
+``used_range`` is emcee's discard / thin arithmetic.  A ``ChainView`` says where the used samples lie in a float64
+device tensor and carries the stream and allocator the summary works with.  ``device_moments`` and
+``device_percentiles`` are the two summaries that any view has (bisip_chain_moments_dev,
+bisip_chain_percentiles_dev); the others are in bisip_amd.autocorr, bisip_amd.histogram and
+bisip_amd.decomposition.
+"""
+
+import numpy as np
+
+__all__ = ('used_range', 'ChainView', 'device_moments', 'device_percentiles')
+
+
+def used_range(n_total, discard, thin):
+    """``(first, n)``: index of the first and number of the samples that ``get_chain(discard, thin)`` keeps of
+    ``n_total`` stored ones, ``first`` and every ``thin``-th after it (emcee).  ValueError when there are none."""
+    n_total, discard, thin = int(n_total), int(discard), int(thin)
+    first = discard + thin - 1
+    n = len(range(first, n_total, thin)) if thin >= 1 and discard >= 0 else 0
+    if n < 1:
+        raise ValueError(f'no samples left with discard={discard}, thin={thin} of {n_total} stored')
+    return first, n
+
+
+class ChainView:
+    """Samples ``offset``, ``offset + stride``, ... (in doubles, ``n`` of them) of a float64 device tensor whose
+    samples hold ``(n_ensembles * walkers_per_ensemble, ndim)`` rows.  ``stride``: None for a contiguous tensor of
+    whole samples.  ``backend``: a HipStretchBackend (its stream and allocator), else torch's current stream on the
+    tensor's device."""
+
+    __slots__ = ('tensor', 'n', 'n_ensembles', 'walkers_per_ensemble', 'ndim', 'offset', 'stride', 'backend')
+
+    def __init__(self, tensor, n, n_ensembles, walkers_per_ensemble, ndim, offset=0, stride=None, backend=None):
+        import torch
+        if not isinstance(tensor, torch.Tensor) or not tensor.is_cuda or tensor.dtype != torch.float64:
+            raise TypeError('the chain must be a float64 tensor on the GPU')
+        n, E, Wp, ndim, offset = int(n), int(n_ensembles), int(walkers_per_ensemble), int(ndim), int(offset)
+        if n < 1:
+            raise ValueError('no samples')
+        row = E * Wp * ndim
+        if stride is None:
+            if not tensor.is_contiguous():
+                raise ValueError('a chain that is not contiguous needs an explicit sample_stride')
+            stride = row
+        stride = int(stride)
+        if stride < row or offset < 0 or offset + (n - 1) * stride + row > tensor.numel():
+            raise ValueError('the samples asked for lie outside the chain tensor')
+        self.tensor, self.n, self.n_ensembles, self.walkers_per_ensemble, self.ndim = tensor, n, E, Wp, ndim
+        self.offset, self.stride, self.backend = offset, stride, backend
+
+    @classmethod
+    def of_tensor(cls, x):
+        """One ensemble: every sample of a device tensor ``(n, walkers, ndim)``, copied first if not contiguous."""
+        n, Wp, ndim = x.shape
+        return cls(x.contiguous(), n, 1, Wp, ndim)
+
+    def derived(self, tensor):
+        """The view of every sample of a new contiguous tensor ``(n, n_ensembles * walkers_per_ensemble, k)`` of
+        quantities derived row by row from this one's samples, on the same backend."""
+        return ChainView(tensor, self.n, self.n_ensembles, self.walkers_per_ensemble, tensor.shape[-1],
+                         backend=self.backend)
+
+    @property
+    def ptr(self):
+        return self.tensor.data_ptr() + 8 * self.offset
+
+    @property
+    def stream(self):
+        if self.backend is not None:
+            return self.backend.stream()
+        import torch
+        return torch.cuda.current_stream(self.tensor.device).cuda_stream
+
+    def synchronize(self):
+        if self.backend is not None:
+            return self.backend.synchronize()
+        import torch
+        torch.cuda.current_stream(self.tensor.device).synchronize()
+
+    def empty(self, shape, dtype):
+        if self.backend is not None:
+            return self.backend.empty(shape, dtype)
+        import torch
+        return torch.empty(shape, dtype=dtype, device=self.tensor.device)
+
+    def upload(self, array):
+        import torch
+        a = np.array(array, dtype=np.float64, order='C')      # (a writable copy: broadcast views are read-only)
+        t = self.empty(a.shape, torch.float64)
+        t.copy_(torch.from_numpy(a))
+        return t
+
+    def samples(self):
+        """The used samples as a strided tensor ``(n, n_ensembles * walkers_per_ensemble, ndim)``: no copy."""
+        import torch
+        t = self.tensor
+        return torch.as_strided(t, (self.n, self.n_ensembles * self.walkers_per_ensemble, self.ndim),
+                                (self.stride, self.ndim, 1), t.storage_offset() + self.offset)
+
+
+def device_moments(view):
+    """``np.mean`` / ``np.std`` over every ensemble's samples of a view: ``(mean, std)``, ``(n_ensembles, ndim)``
+    each (NumPy)."""
+    import torch
+    from . import _hip
+    n, E, Wp, ndim = view.n, view.n_ensembles, view.walkers_per_ensemble, view.ndim
+    mean, std = view.empty((E, ndim), torch.float64), view.empty((E, ndim), torch.float64)
+    work = view.empty((max(1, _hip.chain_moments_workspace(n, E, ndim)),), torch.float64)
+    _hip.chain_moments_dev(view.ptr, n, view.stride, E, Wp, ndim, mean.data_ptr(), std.data_ptr(), work.data_ptr(),
+                           view.stream)
+    view.synchronize()
+    return mean.cpu().numpy(), std.cpu().numpy()
+
+
+def device_percentiles(view, p):
+    """``np.percentile`` over every ensemble's samples of a view, sorted and interpolated on the device:
+    ``(len(p), n_ensembles, ndim)`` (NumPy)."""
+    import torch
+    from . import _hip
+    n, E, Wp, ndim = view.n, view.n_ensembles, view.walkers_per_ensemble, view.ndim
+    p = np.atleast_1d(np.asarray(p, dtype=np.float64))
+    nbytes = _hip.chain_percentiles_workspace(n, E, Wp, ndim, p.size)
+    if nbytes <= 0:
+        raise ValueError('chain too large for one device sort (more than 2^31 values); thin it or use get_chain()')
+    work = view.empty((nbytes,), torch.uint8)
+    out = view.empty((p.size, E, ndim), torch.float64)
+    _hip.chain_percentiles_dev(view.ptr, n, view.stride, E, Wp, ndim, p, out.data_ptr(), work.data_ptr(), nbytes,
+                               view.stream)
+    view.synchronize()
+    return out.cpu().numpy()

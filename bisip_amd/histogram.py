@@ -11,8 +11,8 @@ Definition (what ``np.histogram`` / ``np.histogram2d`` count for equal-width bin
   either coordinate is left out of that pair only.
 
 ``histogram_by_edges`` and ``pair_histograms_by_edges`` count on the host in NumPy.  The ``device_*`` functions run
-``bisip_chain_range_dev`` / ``bisip_chain_histograms_dev`` / ``bisip_chain_pair_histograms_dev`` on a float64 chain
-tensor on the GPU.  Both give the same integers.
+``bisip_chain_range_dev`` / ``bisip_chain_histograms_dev`` / ``bisip_chain_pair_histograms_dev`` on a ChainView
+(bisip_amd.chainview) on the GPU.  Both give the same integers.
 
 A ``range`` argument is ``None`` (min and max of the samples, per ensemble and parameter; a non-finite sample raises
 ValueError as NumPy does), ``'bounds'`` (the prior box: the same edges for every spectrum) or an array ``(ndim, 2)``
@@ -184,62 +184,45 @@ def host_pair_histograms(flat, bins=20, rng=None, bounds=None):
 
 
 # -- device drivers ---------------------------------------------------------------------------------------------
-def _prepare(chain, n_samples, n_ensembles, walkers_per_ensemble, ndim, offset, sample_stride, backend):
-    from .decomposition import _check_chain, _device
-    n, E, Wp, ndim = int(n_samples), int(n_ensembles), int(walkers_per_ensemble), int(ndim)
-    stride = _check_chain(chain, n, sample_stride, E * Wp * ndim, int(offset))
-    empty, stream, sync = _device(backend, chain)
-    return n, E, Wp, ndim, stride, chain.data_ptr() + 8 * int(offset), empty, stream, sync
-
-
-def device_param_range(chain, n_samples, n_ensembles, walkers_per_ensemble, ndim, offset=0, sample_stride=None,
-                       backend=None):
-    """``(minmax (n_ensembles, ndim, 2), n_nonfinite (n_ensembles, ndim))`` (NumPy) of samples ``offset``, ``offset +
-    sample_stride``, ... (in doubles) of a float64 device tensor ``chain`` whose samples hold ``(n_ensembles *
-    walkers_per_ensemble, ndim)`` rows.  Min and max are over the finite values.  ``backend``: a HipStretchBackend
-    (its stream and allocator), else torch's."""
+def device_param_range(view):
+    """``(minmax (n_ensembles, ndim, 2), n_nonfinite (n_ensembles, ndim))`` (NumPy) of the samples of a ChainView
+    (bisip_amd.chainview).  Min and max are over the finite values."""
     import torch
     from . import _hip
-    n, E, Wp, ndim, stride, ptr, empty, stream, sync = _prepare(chain, n_samples, n_ensembles, walkers_per_ensemble,
-                                                                ndim, offset, sample_stride, backend)
-    out = empty((E, ndim, 2), torch.float64)
-    bad = empty((E, ndim), torch.int64)
-    _hip.chain_range_dev(ptr, n, stride, E, Wp, ndim, out.data_ptr(), bad.data_ptr(), stream)
-    sync()
+    E, ndim = view.n_ensembles, view.ndim
+    out = view.empty((E, ndim, 2), torch.float64)
+    bad = view.empty((E, ndim), torch.int64)
+    _hip.chain_range_dev(view.ptr, view.n, view.stride, E, view.walkers_per_ensemble, ndim, out.data_ptr(),
+                         bad.data_ptr(), view.stream)
+    view.synchronize()
     return out.cpu().numpy(), bad.cpu().numpy()
 
 
-def _device_counts(entry, shape_of, chain, edges, n_samples, n_ensembles, walkers_per_ensemble, ndim, offset,
-                   sample_stride, backend):
+def _device_counts(entry, shape_of, view, edges):
     import torch
-    from .decomposition import _upload
-    n, E, Wp, ndim, stride, ptr, empty, stream, sync = _prepare(chain, n_samples, n_ensembles, walkers_per_ensemble,
-                                                                ndim, offset, sample_stride, backend)
+    E, ndim = view.n_ensembles, view.ndim
     edges = np.asarray(edges, dtype=np.float64)
     if edges.ndim != 3 or edges.shape[:2] != (E, ndim) or edges.shape[2] < 2:
         raise ValueError(f'edges must have shape ({E}, {ndim}, bins + 1), got {edges.shape}')
     bins = edges.shape[2] - 1
-    d_edges = _upload(edges, empty)
-    counts = empty(shape_of(E, ndim, bins), torch.int64)
-    entry(ptr, n, stride, E, Wp, ndim, d_edges.data_ptr(), bins, counts.data_ptr(), stream)
-    sync()
+    d_edges = view.upload(edges)
+    counts = view.empty(shape_of(E, ndim, bins), torch.int64)
+    entry(view.ptr, view.n, view.stride, E, view.walkers_per_ensemble, ndim, d_edges.data_ptr(), bins,
+          counts.data_ptr(), view.stream)
+    view.synchronize()
     return counts.cpu().numpy()
 
 
-def device_histograms(chain, edges, n_samples, n_ensembles, walkers_per_ensemble, ndim, offset=0, sample_stride=None,
-                      backend=None):
-    """Counts ``(n_ensembles, ndim, bins)`` int64 (NumPy) of the used samples of a device chain (conventions of
-    device_param_range) within ``edges (n_ensembles, ndim, bins + 1)``, counted where the chain lies."""
+def device_histograms(view, edges):
+    """Counts ``(n_ensembles, ndim, bins)`` int64 (NumPy) of the samples of a ChainView within ``edges (n_ensembles,
+    ndim, bins + 1)``, counted where the chain lies."""
     from . import _hip
-    return _device_counts(_hip.chain_histograms_dev, lambda E, d, b: (E, d, b), chain, edges, n_samples, n_ensembles,
-                          walkers_per_ensemble, ndim, offset, sample_stride, backend)
+    return _device_counts(_hip.chain_histograms_dev, lambda E, d, b: (E, d, b), view, edges)
 
 
-def device_pair_histograms(chain, edges, n_samples, n_ensembles, walkers_per_ensemble, ndim, offset=0,
-                           sample_stride=None, backend=None):
+def device_pair_histograms(view, edges):
     """Counts ``(n_ensembles, npairs, bins, bins)`` int64 (NumPy) of every pair of parameters, ``pair_index`` order."""
     from . import _hip
-    if int(ndim) < 2:
+    if view.ndim < 2:
         raise ValueError('pair histograms need at least two parameters')
-    return _device_counts(_hip.chain_pair_histograms_dev, lambda E, d, b: (E, d * (d - 1) // 2, b, b), chain, edges,
-                          n_samples, n_ensembles, walkers_per_ensemble, ndim, offset, sample_stride, backend)
+    return _device_counts(_hip.chain_pair_histograms_dev, lambda E, d, b: (E, d * (d - 1) // 2, b, b), view, edges)

@@ -19,6 +19,7 @@ import numpy as np
 from . import _hip
 from . import decomposition as _decomp
 from . import utils as _utils
+from .chainview import ChainView, device_moments, device_percentiles, used_range
 from .plotlib import plotlib as _plotlib
 from .sampler import DeviceEnsembleSampler, EnsembleSampler
 
@@ -386,19 +387,16 @@ class PolynomialDecomposition(Inversion):
         return _decomp.integrating_params(theta, self.log_tau, self._data['norm_factor'])
 
     def _decomposition_samples(self, chain, kwargs):
-        """The samples to summarise, on the device: ``(tensor, n, walkers, offset, stride, backend)`` (offset and
-        stride in doubles).  The fitted chain with ``discard`` / ``thin`` (where it lies, or an upload of the used
-        samples), or a flat ``chain`` array -- with the rules of get_param_mean (parse_chain)."""
+        """The samples to summarise, on the device, as a ChainView (bisip_amd.chainview).  The fitted chain with
+        ``discard`` / ``thin`` (where it lies, or an upload of the used samples), or a flat ``chain`` array -- with
+        the rules of get_param_mean (parse_chain)."""
         import torch
         ndim = len(self.params)
         s = self._device_chain_sampler(chain, kwargs)
         if s is not None:
-            t, n, offset, stride = s.used_samples_dev(kwargs.get('discard', 0), kwargs.get('thin', 1))
-            return t, n, s.nwalkers, offset, stride, s.backend
+            return s.used_samples_dev(kwargs.get('discard', 0), kwargs.get('thin', 1))
         if chain is None:
-            discard, thin = int(kwargs.get('discard', 0)), int(kwargs.get('thin', 1))
-            if thin < 1 or discard < 0:
-                raise ValueError(f'no samples left with discard={discard}, thin={thin}')
+            used_range(self.sampler.iteration, kwargs.get('discard', 0), kwargs.get('thin', 1))
         chain = chain if chain is None else np.asarray(chain, dtype=np.float64)
         flat = np.ascontiguousarray(self.parse_chain(chain, **dict(kwargs)), dtype=np.float64)
         if flat.ndim != 2 or flat.shape[1] != ndim:
@@ -409,44 +407,36 @@ class PolynomialDecomposition(Inversion):
         # rows of whole samples (get_chain(flat=True)) keep the sample x walker shape: same bits as the chain itself
         Wp = W if flat.shape[0] % W == 0 else flat.shape[0]
         t = torch.from_numpy(flat).to(torch.device('cuda', self.device))
-        return t, flat.shape[0] // Wp, Wp, 0, Wp * ndim, None
+        return ChainView(t, flat.shape[0] // Wp, 1, Wp, ndim)
 
-    def _integrating_chain_dev(self, chain, kwargs):
-        t, n, Wp, offset, stride, be = self._decomposition_samples(chain, kwargs)
-        d = _decomp.device_integrating_chain(t, n, 1, Wp, len(self.params), self.log_tau, self._data['norm_factor'],
-                                             offset=offset, sample_stride=stride, backend=be)
-        return d, Wp, be
+    def _integrating_view(self, chain, kwargs):
+        view = self._decomposition_samples(chain, kwargs)
+        return view.derived(_decomp.device_integrating_chain(view, self.log_tau, self._data['norm_factor']))
 
     def get_integrating_chain(self, chain=None, **kwargs):
         """``(m_total, log_tau_mean, m_norm)`` of every sample, computed on the GPU: ``(n', nwalkers, 3)`` as
         get_chain; ``(n, 3)`` with ``flat=True`` or for a ``chain`` array."""
         flat = bool(kwargs.get('flat', False)) or chain is not None
-        d, _, _ = self._integrating_chain_dev(chain, kwargs)
-        out = d.cpu().numpy()
+        out = self._integrating_view(chain, kwargs).tensor.cpu().numpy()
         return out.reshape(-1, 3) if flat else out
 
     def get_integrating_mean(self, chain=None, **kwargs):
         """Posterior mean of ``(m_total, log_tau_mean, m_norm)``: ``(3,)`` (kwargs as get_param_mean)."""
-        d, Wp, be = self._integrating_chain_dev(chain, kwargs)
-        return _decomp.device_integrating_moments(d, 1, Wp, backend=be)[0][0]
+        return device_moments(self._integrating_view(chain, kwargs))[0][0]
 
     def get_integrating_std(self, chain=None, **kwargs):
         """Posterior standard deviation of ``(m_total, log_tau_mean, m_norm)``: ``(3,)``."""
-        d, Wp, be = self._integrating_chain_dev(chain, kwargs)
-        return _decomp.device_integrating_moments(d, 1, Wp, backend=be)[1][0]
+        return device_moments(self._integrating_view(chain, kwargs))[1][0]
 
     def get_integrating_percentile(self, p=[2.5, 50, 97.5], chain=None, **kwargs):
         """Percentiles of ``(m_total, log_tau_mean, m_norm)``: ``(len(p), 3)``, ``(3,)`` for a scalar ``p``."""
-        d, Wp, be = self._integrating_chain_dev(chain, kwargs)
-        out = _decomp.device_integrating_percentiles(d, p, 1, Wp, backend=be)[:, 0, :]
+        out = device_percentiles(self._integrating_view(chain, kwargs), p)[:, 0, :]
         return out if np.ndim(p) else out[0]
 
     def get_rtd_percentile(self, p=[2.5, 50, 97.5], chain=None, **kwargs):
         """Percentiles of the RTD ``m_l`` over the chain -- the band of the tutorial's RTD plot: ``(len(p), L)``,
         ``(L,)`` for a scalar ``p``."""
-        t, n, Wp, offset, stride, be = self._decomposition_samples(chain, kwargs)
-        out = _decomp.device_rtd_percentiles(t, p, n, 1, Wp, len(self.params), self.log_tau, offset=offset,
-                                             sample_stride=stride, backend=be)[:, 0, :]
+        out = _decomp.device_rtd_percentiles(self._decomposition_samples(chain, kwargs), p, self.log_tau)[:, 0, :]
         return out if np.ndim(p) else out[0]
 
 

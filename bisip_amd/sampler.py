@@ -40,6 +40,7 @@ import os
 
 import numpy as np
 
+from .chainview import ChainView, device_moments, device_percentiles, used_range
 from .dist import all_gather_rows, shard_range
 
 
@@ -1455,30 +1456,32 @@ class DeviceEnsembleSampler(_SamplerBase):
             parts[:] = [_DeviceSlabs(t for p in parts for t in p.tensors)]
         return parts[0].tensor()
 
+    def used_samples_dev(self, discard=0, thin=1, upload=True):
+        """``get_chain(discard, thin)`` on the device as a ChainView (bisip_amd.chainview): the stored chain itself
+        with ``chain_on_device``, else an upload of the used samples only -- or, with ``upload=False``,
+        device_chain()'s AttributeError."""
+        E, Wp, W, ndim = self.n_ensembles, self.walkers_per_ensemble, self.nwalkers, self.ndim
+        if self.chain_on_device or not upload:
+            t = self.device_chain()
+            first, n = used_range(t.shape[0], discard, thin)
+            return ChainView(t, n, E, Wp, ndim, first * W * ndim, int(thin) * W * ndim, self.backend)
+        import torch
+        _, n = used_range(self.iteration, discard, thin)
+        used = torch.from_numpy(np.ascontiguousarray(self.get_chain(discard=int(discard), thin=int(thin))))
+        return ChainView(used.to(self.backend.device), n, E, Wp, ndim, backend=self.backend)
+
     def param_moments(self, discard=0, thin=1):
-        """Mean and standard deviation of every parameter over
-        ``chain[discard + thin - 1::thin]`` flattened over the walkers of each ensemble --
-        ``np.mean`` / ``np.std`` of ``get_chain(discard, thin, flat=True)`` (reference:
+        """Mean and standard deviation of every parameter over the used samples, flattened over the walkers of each
+        ensemble -- ``np.mean`` / ``np.std`` of ``get_chain(discard, thin, flat=True)`` (reference:
         src/bisip/utils.py:55-85) -- computed on the device, only the two
         ``(n_ensembles, ndim)`` results come back.  Returns ``(mean, std)``."""
-        import torch
-        from . import _hip
-        t = self.device_chain()
-        n_total, W, ndim = (int(x) for x in t.shape)
-        discard, thin = int(discard), int(thin)
-        first = discard + thin - 1
-        n = len(range(first, n_total, thin))
-        if thin < 1 or discard < 0 or n < 1:
-            raise ValueError(f'no samples left with discard={discard}, thin={thin} of {n_total} stored')
-        be = self.backend
-        E, Wp = self.n_ensembles, self.walkers_per_ensemble
-        mean = be.empty((E, ndim), torch.float64)
-        std = be.empty((E, ndim), torch.float64)
-        work = be.empty((max(1, _hip.chain_moments_workspace(n, E, ndim)),), torch.float64)
-        _hip.chain_moments_dev(t.data_ptr() + 8 * first * W * ndim, n, thin * W * ndim, E, Wp, ndim,
-                               mean.data_ptr(), std.data_ptr(), work.data_ptr(), be.stream())
-        be.synchronize()
-        return mean.cpu().numpy(), std.cpu().numpy()
+        return device_moments(self.used_samples_dev(discard, thin, upload=False))
+
+    def param_percentiles(self, p=(2.5, 50, 97.5), discard=0, thin=1):
+        """``np.percentile(get_chain(discard, thin, flat=True), p, axis=0)`` per ensemble
+        (reference: src/bisip/utils.py:37-53), sorted and interpolated on the device; returns
+        ``(len(p), n_ensembles, ndim)``."""
+        return device_percentiles(self.used_samples_dev(discard, thin, upload=False), p)
 
     def get_autocorr_time(self, discard=0, thin=1, c=5, tol=50, quiet=False):
         """emcee's integrated autocorrelation time of ``get_chain(discard, thin)``, times ``thin``, every
@@ -1486,72 +1489,30 @@ class DeviceEnsembleSampler(_SamplerBase):
         lies (``chain_on_device``), else from an upload of the used samples only.  ``(ndim,)`` for one ensemble,
         ``(n_ensembles, ndim)`` for a batch.  The ``tol`` test is that of integrated_time, per ensemble (every
         ensemble has the same number of samples); the AutocorrError carries every estimate."""
-        import torch
         from .autocorr import check_c, check_tol, device_integrated_time
         c = check_c(c)
-        discard, thin = int(discard), int(thin)
-        E, Wp, W, ndim = self.n_ensembles, self.walkers_per_ensemble, self.nwalkers, self.ndim
-        be = self.backend
-        if self.chain_on_device:
-            t = self.device_chain()
-            n_total = int(t.shape[0])
-        else:
-            n_total = self.iteration
-        first = discard + thin - 1
-        n = len(range(first, n_total, thin)) if thin >= 1 and discard >= 0 else 0
-        if n < 1:
-            raise ValueError(f'no samples left with discard={discard}, thin={thin} of {n_total} stored')
-        if self.chain_on_device:
-            tau, _ = device_integrated_time(t, n, E, Wp, ndim, c, offset=first * W * ndim,
-                                            sample_stride=thin * W * ndim, backend=be)
-        else:
-            used = torch.from_numpy(np.ascontiguousarray(self.get_chain(discard=discard, thin=thin))).to(be.device)
-            tau, _ = device_integrated_time(used, n, E, Wp, ndim, c, sample_stride=W * ndim, backend=be)
+        view = self.used_samples_dev(discard, thin)
+        tau, _ = device_integrated_time(view, c)
+        E = self.n_ensembles
         what = 'parameter(s)' if E == 1 else f'(ensemble, parameter) pair(s) of {E} ensembles'
-        tau = check_tol(tau if E > 1 else tau[0], n, tol, quiet, what)
-        return thin * tau
-
-    def used_samples_dev(self, discard=0, thin=1):
-        """``get_chain(discard, thin)`` on the device as ``(tensor, n, offset, sample_stride)`` (offset and stride
-        in doubles): the stored chain itself with ``chain_on_device``, else an upload of the used samples only."""
-        import torch
-        discard, thin = int(discard), int(thin)
-        W, ndim = self.nwalkers, self.ndim
-        if self.chain_on_device:
-            t = self.device_chain()
-            n_total = int(t.shape[0])
-        else:
-            n_total = self.iteration
-        first = discard + thin - 1
-        n = len(range(first, n_total, thin)) if thin >= 1 and discard >= 0 else 0
-        if n < 1:
-            raise ValueError(f'no samples left with discard={discard}, thin={thin} of {n_total} stored')
-        if self.chain_on_device:
-            return t, n, first * W * ndim, thin * W * ndim
-        used = torch.from_numpy(np.ascontiguousarray(self.get_chain(discard=discard, thin=thin))).to(self.backend.device)
-        return used, n, 0, W * ndim
+        tau = check_tol(tau if E > 1 else tau[0], view.n, tol, quiet, what)
+        return int(thin) * tau
 
     def param_range(self, discard=0, thin=1):
         """Min and max of the finite values of every parameter over ``get_chain(discard, thin)`` per ensemble,
         ``(n_ensembles, ndim, 2)``, and how many of its values are not finite, ``(n_ensembles, ndim)``, taken on the
         device (bisip_chain_range_dev)."""
         from .histogram import device_param_range
-        t, n, offset, stride = self.used_samples_dev(discard, thin)
-        return device_param_range(t, n, self.n_ensembles, self.walkers_per_ensemble, self.ndim, offset=offset,
-                                  sample_stride=stride, backend=self.backend)
+        return device_param_range(self.used_samples_dev(discard, thin))
 
     def _histogram_edges(self, bins, range, discard, thin, bounds):
-        """The used samples on the device and the edges ``(n_ensembles, ndim, bins + 1)`` of a ``range`` argument
-        (None, 'bounds' or an array: bisip_amd.histogram)."""
+        """The used samples on the device (a ChainView) and the edges ``(n_ensembles, ndim, bins + 1)`` of a
+        ``range`` argument (None, 'bounds' or an array: bisip_amd.histogram)."""
         from . import histogram as hg
         bins = hg.check_bins(bins)
-        E, Wp, ndim = self.n_ensembles, self.walkers_per_ensemble, self.ndim
-        used = self.used_samples_dev(discard, thin)
-        t, n, offset, stride = used
-
-        def data_range():
-            return hg.device_param_range(t, n, E, Wp, ndim, offset=offset, sample_stride=stride, backend=self.backend)
-        return used, hg.edges_from_range(hg.resolve_range(range, E, ndim, bounds, data_range), bins)
+        view = self.used_samples_dev(discard, thin)
+        r = hg.resolve_range(range, view.n_ensembles, view.ndim, bounds, lambda: hg.device_param_range(view))
+        return view, hg.edges_from_range(r, bins)
 
     def param_histograms(self, bins=25, range=None, discard=0, thin=1, bounds=None):
         """``np.histogram`` of every parameter of every ensemble over ``get_chain(discard, thin, flat=True)`` -- the
@@ -1561,10 +1522,8 @@ class DeviceEnsembleSampler(_SamplerBase):
         or an array ``(ndim, 2)`` / ``(n_ensembles, ndim, 2)``.  Returns ``(counts (n_ensembles, ndim, bins) int64, edges
         (n_ensembles, ndim, bins + 1))``."""
         from .histogram import device_histograms
-        (t, n, offset, stride), edges = self._histogram_edges(bins, range, discard, thin, bounds)
-        counts = device_histograms(t, edges, n, self.n_ensembles, self.walkers_per_ensemble, self.ndim, offset=offset,
-                                   sample_stride=stride, backend=self.backend)
-        return counts, edges
+        view, edges = self._histogram_edges(bins, range, discard, thin, bounds)
+        return device_histograms(view, edges), edges
 
     def pair_histograms(self, bins=20, range=None, discard=0, thin=1, bounds=None):
         """``np.histogram2d`` of every pair of parameters of every ensemble -- the panels of the reference's
@@ -1573,39 +1532,33 @@ class DeviceEnsembleSampler(_SamplerBase):
         ``pairs = np.triu_indices(ndim, 1)``; ``counts[e, q, a, b]``: parameter ``pairs[0][q]`` in bin ``a``,
         ``pairs[1][q]`` in bin ``b``."""
         from .histogram import device_pair_histograms, pair_index
-        (t, n, offset, stride), edges = self._histogram_edges(bins, range, discard, thin, bounds)
-        counts = device_pair_histograms(t, edges, n, self.n_ensembles, self.walkers_per_ensemble, self.ndim,
-                                        offset=offset, sample_stride=stride, backend=self.backend)
-        return counts, edges, pair_index(self.ndim)
+        view, edges = self._histogram_edges(bins, range, discard, thin, bounds)
+        return device_pair_histograms(view, edges), edges, pair_index(self.ndim)
+
+    def _integrating_view(self, log_tau, norm_factor, discard, thin):
+        from .decomposition import device_integrating_chain
+        view = self.used_samples_dev(discard, thin)
+        return view.derived(device_integrating_chain(view, log_tau, norm_factor))
 
     def integrating_chain_dev(self, log_tau, norm_factor, discard=0, thin=1):
         """PolynomialDecomposition's ``(m_total, log_tau_mean, m_norm)`` of every sample of ``get_chain(discard,
         thin)`` (bisip_rtd_integrals_dev; bisip_amd.decomposition): a device tensor ``(n, nwalkers, 3)``.
         ``norm_factor``: scalar or one per ensemble."""
-        from .decomposition import device_integrating_chain
-        t, n, offset, stride = self.used_samples_dev(discard, thin)
-        return device_integrating_chain(t, n, self.n_ensembles, self.walkers_per_ensemble, self.ndim, log_tau,
-                                        norm_factor, offset=offset, sample_stride=stride, backend=self.backend)
+        return self._integrating_view(log_tau, norm_factor, discard, thin).tensor
 
     def integrating_moments(self, log_tau, norm_factor, discard=0, thin=1):
         """Mean and std of the integrating parameters per ensemble, ``(n_ensembles, 3)`` each, on the device."""
-        from .decomposition import device_integrating_moments
-        d = self.integrating_chain_dev(log_tau, norm_factor, discard, thin)
-        return device_integrating_moments(d, self.n_ensembles, self.walkers_per_ensemble, backend=self.backend)
+        return device_moments(self._integrating_view(log_tau, norm_factor, discard, thin))
 
     def integrating_percentiles(self, p, log_tau, norm_factor, discard=0, thin=1):
         """np.percentile of the integrating parameters per ensemble, ``(len(p), n_ensembles, 3)``, on the device."""
-        from .decomposition import device_integrating_percentiles
-        d = self.integrating_chain_dev(log_tau, norm_factor, discard, thin)
-        return device_integrating_percentiles(d, p, self.n_ensembles, self.walkers_per_ensemble, backend=self.backend)
+        return device_percentiles(self._integrating_view(log_tau, norm_factor, discard, thin), p)
 
     def rtd_percentiles(self, p, log_tau, discard=0, thin=1):
         """np.percentile of the RTD ``m_l`` per ensemble, ``(len(p), n_ensembles, L)``, on the device
         (bisip_rtd_columns_dev, then the selection of bisip_columns_percentiles_dev)."""
         from .decomposition import device_rtd_percentiles
-        t, n, offset, stride = self.used_samples_dev(discard, thin)
-        return device_rtd_percentiles(t, p, n, self.n_ensembles, self.walkers_per_ensemble, self.ndim, log_tau,
-                                      offset=offset, sample_stride=stride, backend=self.backend)
+        return device_rtd_percentiles(self.used_samples_dev(discard, thin), p, log_tau)
 
     def model_percentiles(self, p=(2.5, 50, 97.5), discard=0, thin=1):
         """``np.percentile(forward(get_chain(discard, thin, flat=True)), p, axis=0)`` -- the
@@ -1617,12 +1570,7 @@ class DeviceEnsembleSampler(_SamplerBase):
         from . import _hip
         if self.n_ensembles != 1:
             raise NotImplementedError('model percentiles of a batch of spectra: one spectrum at a time')
-        t = self.device_chain()
-        n_total = int(t.shape[0])
-        discard, thin = int(discard), int(thin)
-        if thin < 1 or discard < 0 or len(range(discard + thin - 1, n_total, thin)) < 1:
-            raise ValueError(f'no samples left with discard={discard}, thin={thin} of {n_total} stored')
-        rows = t[discard + thin - 1::thin].reshape(-1, self.ndim).contiguous()
+        rows = self.used_samples_dev(discard, thin, upload=False).samples().reshape(-1, self.ndim).contiguous()
         be, ctx = self.backend, self.backend.ctx
         p = np.atleast_1d(np.asarray(p, dtype=np.float64))
         n, cols = int(rows.shape[0]), 2 * ctx.N
@@ -1632,29 +1580,3 @@ class DeviceEnsembleSampler(_SamplerBase):
         _hip.columns_percentiles_dev(Zc.data_ptr(), cols, n, p, out.data_ptr(), be.stream())
         be.synchronize()
         return out.cpu().numpy().reshape(p.size, 2, ctx.N)
-
-    def param_percentiles(self, p=(2.5, 50, 97.5), discard=0, thin=1):
-        """``np.percentile(get_chain(discard, thin, flat=True), p, axis=0)`` per ensemble
-        (reference: src/bisip/utils.py:37-53), sorted and interpolated on the device; returns
-        ``(len(p), n_ensembles, ndim)``."""
-        import torch
-        from . import _hip
-        t = self.device_chain()
-        n_total, W, ndim = (int(x) for x in t.shape)
-        discard, thin = int(discard), int(thin)
-        first = discard + thin - 1
-        n = len(range(first, n_total, thin))
-        if thin < 1 or discard < 0 or n < 1:
-            raise ValueError(f'no samples left with discard={discard}, thin={thin} of {n_total} stored')
-        p = np.atleast_1d(np.asarray(p, dtype=np.float64))
-        be = self.backend
-        E, Wp = self.n_ensembles, self.walkers_per_ensemble
-        nbytes = _hip.chain_percentiles_workspace(n, E, Wp, ndim, p.size)
-        if nbytes <= 0:
-            raise ValueError('chain too large for one device sort (more than 2^31 values); thin it or use get_chain()')
-        work = be.empty((nbytes,), torch.uint8)
-        out = be.empty((p.size, E, ndim), torch.float64)
-        _hip.chain_percentiles_dev(t.data_ptr() + 8 * first * W * ndim, n, thin * W * ndim, E, Wp, ndim, p,
-                                   out.data_ptr(), work.data_ptr(), nbytes, be.stream())
-        be.synchronize()
-        return out.cpu().numpy()

@@ -208,6 +208,7 @@ def test_cfg5_slice_full_size():
     random spectra against the host function."""
     import torch
     from bisip_amd.autocorr import device_integrated_time
+    from bisip_amd.chainview import ChainView
     E, Wp, ndim, n_total, discard = 512, 256, 7, 1000, 500
     g = torch.Generator(device='cuda').manual_seed(0)
     rho = torch.linspace(0.0, 0.97, E * ndim, dtype=torch.float64, device='cuda').reshape(E, 1, ndim)
@@ -217,8 +218,8 @@ def test_cfg5_slice_full_size():
     for s in range(1, n_total):
         chain[s] = rho * chain[s - 1] + torch.randn((E * Wp, ndim), generator=g, dtype=torch.float64, device='cuda')
     W = E * Wp
-    tau, win = device_integrated_time(chain, n_total - discard, E, Wp, ndim, 5.0, offset=discard * W * ndim,
-                                      sample_stride=W * ndim)
+    tau, win = device_integrated_time(ChainView(chain, n_total - discard, E, Wp, ndim, offset=discard * W * ndim,
+                                                stride=W * ndim), 5.0)
     assert np.isfinite(tau).all() and (win >= 1).all()
     for e in np.random.default_rng(0).choice(E, 8, replace=False):
         x = chain[discard:, e * Wp:(e + 1) * Wp].cpu().numpy()

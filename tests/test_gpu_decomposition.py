@@ -55,8 +55,8 @@ def chain_columns(t, n, off, stride, E, Wp, ndim, log_tau):
 
 def rtd_columns(s, log_tau, discard, thin):
     """Every m_l of every used sample of a sampler: (E, L, n * Wp)."""
-    t, n, off, stride = s.used_samples_dev(discard, thin)
-    return chain_columns(t, n, off, stride, s.n_ensembles, s.walkers_per_ensemble, s.ndim, log_tau)
+    v = s.used_samples_dev(discard, thin)
+    return chain_columns(v.tensor, v.n, v.offset, v.stride, s.n_ensembles, s.walkers_per_ensemble, s.ndim, log_tau)
 
 
 def batch_spectra():
@@ -122,19 +122,21 @@ def test_many_percentiles_of_many_ensembles_take_the_sort_path():
     """24 ensembles x 3 = 72 columns and 13 percentiles: bisip_chain_percentiles_dev sorts."""
     import torch
     from bisip_amd import decomposition
+    from bisip_amd.chainview import ChainView, device_moments, device_percentiles
     E, Wp, n, P = 24, 16, 40, 5
     rng = np.random.default_rng(5)
     chain = prior_rows(rng, n * E * Wp, P).reshape(n, E * Wp, P + 2)
     lt = np.linspace(-7.0, 3.0, 64)
     nf = rng.uniform(0.5, 3.0, E)
     t = torch.from_numpy(chain).cuda()
-    d = decomposition.device_integrating_chain(t, n, E, Wp, P + 2, lt, nf)
+    view = ChainView(t, n, E, Wp, P + 2)
+    d = decomposition.device_integrating_chain(view, lt, nf)
     got = d.cpu().numpy().reshape(n, E, Wp, 3)
     want, b3, _, _ = derived_yardstick(chain.reshape(n, E, Wp, P + 2), lt, nf[None, :, None])
     for j in range(3):
         assert_within(got[..., j], want[..., j], b3[..., j])
-    mean, std = decomposition.device_integrating_moments(d, E, Wp)
-    pct = decomposition.device_integrating_percentiles(d, P_MANY, E, Wp)
+    mean, std = device_moments(view.derived(d))
+    pct = device_percentiles(view.derived(d), P_MANY)
     gf = got.transpose(1, 0, 2, 3).reshape(E, -1, 3)
     wf = want.transpose(1, 0, 2, 3).reshape(E, -1, 3)
     bf = b3.transpose(1, 0, 2, 3).reshape(E, -1, 3)
@@ -159,9 +161,9 @@ def test_flat_chain_of_prior_box_rows(P):
     check_summaries(got, want, b3, mean, std, pct, P_MANY)
     assert m.get_integrating_percentile(97.5, chain=rows).shape == (3,)
     # every m_l of every row, on the layout the chain= path uploads (5000 rows: one sample of 5000 walkers)
-    t, n, Wp, off, stride, _ = m._decomposition_samples(rows, {})
-    assert (n, Wp) == (1, 5000)
-    cols = chain_columns(t, n, off, stride, 1, Wp, P + 2, m.log_tau)[0]          # (L, 5000)
+    v = m._decomposition_samples(rows, {})
+    assert (v.n, v.walkers_per_ensemble) == (1, 5000)
+    cols = chain_columns(v.tensor, v.n, v.offset, v.stride, 1, v.walkers_per_ensemble, P + 2, m.log_tau)[0]          # (L, 5000)
     assert_within(cols.T, m_want, bm, 'm_l')
     rp = m.get_rtd_percentile(chain=rows)
     assert rp.shape == (3, m.log_tau.size)
@@ -281,13 +283,15 @@ def test_more_samples_than_one_grid_column():
     """70,000 samples of 2 x 1 walkers: the kernels' sample loop goes beyond the 65,535 blocks of the grid's y."""
     import torch
     from bisip_amd import decomposition
+    from bisip_amd.chainview import ChainView
     E, Wp, n, P = 2, 1, 70000, 4
     rng = np.random.default_rng(70)
     chain = prior_rows(rng, n * E * Wp, P).reshape(n, E * Wp, P + 2)
     lt = np.linspace(-6.0, 2.0, 40)
     nf = np.array([0.7, 2.5])
     t = torch.from_numpy(chain).cuda()
-    got = decomposition.device_integrating_chain(t, n, E, Wp, P + 2, lt, nf).cpu().numpy().reshape(n, E, Wp, 3)
+    got = decomposition.device_integrating_chain(ChainView(t, n, E, Wp, P + 2), lt, nf).cpu().numpy()
+    got = got.reshape(n, E, Wp, 3)
     want, b3, m_want, bm = derived_yardstick(chain.reshape(n, E, Wp, P + 2), lt, nf[None, :, None])
     for j in range(3):
         assert_within(got[..., j], want[..., j], b3[..., j])

@@ -273,17 +273,19 @@ def test_spectra_batch(model, opts, where):
 def test_range_none_refuses_a_non_finite_sample():
     import torch
     from bisip_amd import histogram as hg
+    from bisip_amd.chainview import ChainView
     t = torch.rand((6, 2 * 10, 3), dtype=torch.float64, device='cuda')
     t[4, 13, 2] = float('nan')
-    minmax, bad = hg.device_param_range(t, 6, 2, 10, 3)
+    view = ChainView(t, 6, 2, 10, 3)
+    minmax, bad = hg.device_param_range(view)
     assert bad.sum() == 1 and bad[1, 2] == 1
     with pytest.raises(ValueError, match='not finite'):
         hg.resolve_range(None, 2, 3, data_range=lambda: (minmax, bad))
     # an explicit range counts the rest
     edges = hg.edges_from_range(hg.resolve_range([[0, 1]] * 3, 2, 3), 10)
-    counts = hg.device_histograms(t, edges, 6, 2, 10, 3)
+    counts = hg.device_histograms(view, edges)
     assert counts[1, 2].sum() == 59 and counts[0].sum() == 180
-    pc = hg.device_pair_histograms(t, edges, 6, 2, 10, 3)
+    pc = hg.device_pair_histograms(view, edges)
     np.testing.assert_array_equal(pc.sum(axis=(2, 3)), [[60, 60, 60], [60, 59, 59]])
 
 
@@ -291,6 +293,7 @@ def test_full_size_cfg5_slice():
     """512 spectra x 256 walkers, 500 used samples of 1000 stored, 7 parameters: a synthetic chain made on the device."""
     import torch
     from bisip_amd import histogram as hg
+    from bisip_amd.chainview import ChainView
     E, Wp, ndim, stored, discard = 512, 256, 7, 1000, 500
     W, n = E * Wp, stored - discard
     g = torch.Generator(device='cuda').manual_seed(2024)
@@ -300,22 +303,22 @@ def test_full_size_cfg5_slice():
         blk = torch.randn((100, E, Wp, ndim), generator=g, dtype=torch.float64, device='cuda')
         t[s0:s0 + 100] = (centre + 0.05 * blk).reshape(100, W, ndim)
         del blk
-    offset, stride = discard * W * ndim, W * ndim
-    minmax, bad = hg.device_param_range(t, n, E, Wp, ndim, offset=offset, sample_stride=stride)
+    view = ChainView(t, n, E, Wp, ndim, offset=discard * W * ndim, stride=W * ndim)
+    minmax, bad = hg.device_param_range(view)
     assert not bad.any()
     edges1 = hg.edges_from_range(minmax, 25)
-    counts = hg.device_histograms(t, edges1, n, E, Wp, ndim, offset=offset, sample_stride=stride)
+    counts = hg.device_histograms(view, edges1)
     assert counts.shape == (E, ndim, 25)
     assert (counts.sum(axis=2) == n * Wp).all()
     edges2 = hg.edges_from_range(minmax, 20)
-    pc = hg.device_pair_histograms(t, edges2, n, E, Wp, ndim, offset=offset, sample_stride=stride)
+    pc = hg.device_pair_histograms(view, edges2)
     assert pc.shape == (E, 21, 20, 20)
     assert (pc.sum(axis=(2, 3)) == n * Wp).all()
     # the prior box of the survey: the same edges for every spectrum, a narrow posterior inside them
     box = np.broadcast_to(np.array([[-1.0, 2.0]] * ndim), (E, ndim, 2))
     eb1, eb2 = hg.edges_from_range(box, 25), hg.edges_from_range(box, 20)
-    cb = hg.device_histograms(t, eb1, n, E, Wp, ndim, offset=offset, sample_stride=stride)
-    pb = hg.device_pair_histograms(t, eb2, n, E, Wp, ndim, offset=offset, sample_stride=stride)
+    cb = hg.device_histograms(view, eb1)
+    pb = hg.device_pair_histograms(view, eb2)
     assert (cb.sum(axis=2) == n * Wp).all() and (pb.sum(axis=(2, 3)) == n * Wp).all()
     for e in (0, 1, 63, 200, 255, 256, 400, 511):
         flat = t[discard:, e * Wp:(e + 1) * Wp].reshape(-1, ndim).cpu().numpy()

@@ -697,6 +697,38 @@ def test_compensated_persistent_kernel_with_and_without_staged_low_words(poly_de
     batch.close()
 
 
+def test_used_samples_dev_is_get_chain_wherever_the_chain_lies():
+    """The ChainView of used_samples_dev addresses get_chain(discard, thin) bit for bit: in the resident chain
+    (chain_on_device) and in the upload of the used samples of a host chain."""
+    import bisip_amd
+    from bisip_amd.synthetic import synthetic_columns
+    E, Wp, stored = 2, 10, 7
+    tables = [synthetic_columns(32, i) for i in range(E)]
+    for where in ('device', 'host'):
+        batch = bisip_amd.SpectraBatch('PolynomialDecomposition', tables, nwalkers=Wp, nsteps=stored, poly_deg=2)
+        np.random.seed(6)
+        batch.fit(seed=8, chain=where)
+        s = batch._sampler
+        assert s.chain_on_device == (where == 'device') and s.n_ensembles == E and s.iteration == stored
+        row = E * Wp * s.ndim
+        for discard, thin in ((0, 1), (2, 2), (1, 3)):
+            want = np.ascontiguousarray(s.get_chain(discard=discard, thin=thin))
+            view = s.used_samples_dev(discard, thin)
+            assert view.n == want.shape[0] == len(range(discard + thin - 1, stored, thin))
+            assert (view.n_ensembles, view.walkers_per_ensemble, view.ndim) == (E, Wp, s.ndim)
+            flat = view.tensor.reshape(-1).cpu().numpy()
+            got = np.stack([flat[view.offset + i * view.stride:][:row] for i in range(view.n)])
+            assert np.array_equal(got.view(np.int64), want.reshape(view.n, row).view(np.int64))
+        with pytest.raises(ValueError, match='no samples left'):
+            s.used_samples_dev(6, 2)
+        with pytest.raises(ValueError, match='no samples left'):
+            s.used_samples_dev(0, 0)
+        if where == 'host':
+            with pytest.raises(AttributeError, match='not resident'):
+                s.used_samples_dev(upload=False)
+        batch.close()
+
+
 def test_persistent_falls_back_when_ensemble_too_large():
     """Beyond one workgroup a single ensemble of up to 8,192 walkers and 7 parameters has the multi-workgroup
     persistent kernel; past either limit persistent=True quietly runs a launch per half-step."""
