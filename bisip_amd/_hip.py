@@ -118,6 +118,11 @@ SYMBOLS = {
     'bisip_chain_pair_histograms_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                        ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                                        ctypes.c_void_p, ctypes.c_void_p]),
+    'bisip_chain_trace_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    'bisip_chain_trace_lds_walkers': (ctypes.c_int, [ctypes.c_int]),
+    'bisip_chain_trace_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                             ctypes.c_int, _dp, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int64, ctypes.c_void_p]),
     'bisip_column_percentiles_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     'bisip_column_percentiles_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, _dp, ctypes.c_int,
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
@@ -772,6 +777,30 @@ def chain_pair_histograms_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles
     _check(load_library().bisip_chain_pair_histograms_dev(d_chain_ptr, int(n_samples), int(sample_stride),
                                                           int(n_ensembles), int(walkers_per_ensemble), int(ndim),
                                                           d_edges_ptr, int(bins), d_counts_ptr, stream))
+
+
+def chain_trace_workspace(n_samples, n_ensembles, walkers_per_ensemble, ndim, n_percentiles):
+    """Bytes of device scratch chain_trace_dev needs (0: none; negative: shape not supported)."""
+    return int(load_library().bisip_chain_trace_workspace(int(n_samples), int(n_ensembles), int(walkers_per_ensemble),
+                                                          int(ndim), int(n_percentiles)))
+
+
+def chain_trace_lds_walkers(ndim):
+    """The largest walkers_per_ensemble that chain_trace_dev sorts in LDS at this ndim (bigger ensembles are gathered
+    into columns first and need the workspace)."""
+    return int(load_library().bisip_chain_trace_lds_walkers(int(ndim)))
+
+
+def chain_trace_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, percentiles,
+                    d_pct_ptr, d_mean_ptr, d_work_ptr=0, work_bytes=0, stream=0):
+    """np.percentile and the mean over the walkers of every (sample, ensemble, parameter): d_pct (len(p), n_samples,
+    n_ensembles, ndim), d_mean (n_samples, n_ensembles, ndim) or 0 / None; ``percentiles``: host array in [0, 100], up
+    to 8, or None / empty for the mean alone.  Device pointers (ints), asynchronous on ``stream``."""
+    p = _c([] if percentiles is None else percentiles).ravel()
+    _check(load_library().bisip_chain_trace_dev(d_chain_ptr or None, int(n_samples), int(sample_stride), int(n_ensembles),
+                                                int(walkers_per_ensemble), int(ndim), _p(p) if p.size else None, p.size,
+                                                d_pct_ptr or None, d_mean_ptr or None, d_work_ptr or None,
+                                                int(work_bytes), stream))
 
 
 def ensemble_gram_workspace(W, ndim):

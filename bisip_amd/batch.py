@@ -241,6 +241,23 @@ class SpectraBatch:
         return self._histogram_sampler().pair_histograms(bins, range, discard=discard, thin=thin,
                                                          bounds=self.param_bounds)
 
+    def get_trace_percentile(self, p=(2.5, 50, 97.5), discard=0, thin=1):
+        """Percentiles over the WALKERS of every spectrum at every step, ``(len(p), n, E, ndim)`` (``(n, E, ndim)`` for a
+        scalar ``p``) -- per spectrum the trace of the reference's plot_traces (src/bisip/plotlib.py:17-54) as numbers --
+        taken on the device for ``chain='device'`` and ``'host'`` alike."""
+        out = self._histogram_sampler().trace_percentiles(p, discard=discard, thin=thin)
+        return out if np.ndim(p) else out[0]
+
+    def get_trace_mean(self, discard=0, thin=1):
+        """The mean over the walkers of every spectrum at every step, ``(n, E, ndim)``."""
+        return self._histogram_sampler().trace_mean(discard=discard, thin=thin)
+
+    def get_log_prob_trace(self, p=(2.5, 50, 97.5), discard=0, thin=1):
+        """Percentiles over the walkers of every spectrum's stored log-probability at every step, ``(len(p), n, E)``
+        (``(n, E)`` for a scalar ``p``): where burn-in shows first."""
+        out = self._histogram_sampler().log_prob_trace(p, discard=discard, thin=thin)
+        return out if np.ndim(p) else out[0]
+
     # -- PolynomialDecomposition: relaxation time distribution and integrating parameters ----------------------
     def _decomposition(self):
         if self.model != 'PolynomialDecomposition':

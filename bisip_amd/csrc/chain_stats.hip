@@ -18,6 +18,7 @@
 // parameter) and plot_corner (:233-259: corner's 1-D and pairwise 2-D histograms) -- are counted at the end of this
 // file (bisip_chain_range_dev, bisip_chain_histograms_dev, bisip_chain_pair_histograms_dev).
 #include "host.h"
+#include "select_key.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -33,6 +34,7 @@ struct GatherArgs {
     long long n_samples, sample_stride, E, Wp;
     int ndim;
     double *cols;   // (E*ndim, n_samples*Wp)
+    int by_sample;  // k_gather_columns_tiled: (n_samples*E*ndim, Wp) instead, one column per (sample, ensemble, parameter)
 };
 
 // one thread per (sample, ensemble, walker): reads its ndim-double row, writes ndim columns
@@ -70,8 +72,9 @@ __global__ __launch_bounds__(256) void k_gather_columns_tiled(const GatherArgs a
         tile[r][q] = src[(long long)r * a.ndim + q];
     }
     __syncthreads();
-    const long long n = a.n_samples * a.Wp;
-    double *__restrict__ dst = a.cols + (e * a.ndim + q0) * n + s * a.Wp + w0;
+    const long long n = a.by_sample ? a.Wp : a.n_samples * a.Wp;
+    double *__restrict__ dst = a.by_sample ? a.cols + ((s * a.E + e) * a.ndim + q0) * n + w0
+                                           : a.cols + (e * a.ndim + q0) * n + s * a.Wp + w0;
     for (int idx = threadIdx.x; idx < nr * nc; idx += 256) {
         const int q = idx / nr, r = idx - q * nr;
         dst[(long long)q * n + r] = tile[r][q];
@@ -120,20 +123,9 @@ struct SelectArgs {
     int n_p;
     long long lo[SEL_MAX_P];   // lower order statistic of each percentile (in the kernarg segment: no upload, no wait)
     double t[SEL_MAX_P];       // weight of the upper one
-    double *out;               // (n_p, columns)
+    double *out;               // (n_p, columns): percentile k of column c at out[k * out_stride + c]
+    long long out_stride;
 };
-
-__device__ __forceinline__ unsigned long long select_key(double v)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);      // ascending keys <=> ascending doubles
-}
-
-__device__ __forceinline__ double select_value(unsigned long long k)
-{
-    const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)u);
-}
 
 // One 1024-lane workgroup per column, narrowing a RANGE of keys and finishing by counting.  VPT > 0: the
 // column is held in REGISTERS (VPT keys per lane, read from memory once); VPT = 0: longer columns are re-read
@@ -208,7 +200,7 @@ void k_segmented_select(const SelectArgs a)
     // get_model_percentile) returns.  Keys of NaNs lie beyond those of the infinities at either end.
     // kmin / kmax are the same in every lane: the whole workgroup leaves here, before any later barrier.
     if (kmax > 0xfff0000000000000ull || kmin < 0x000fffffffffffffull) {
-        if (tid < a.n_p) a.out[(long long)tid * a.columns + col] = __builtin_nan("");
+        if (tid < a.n_p) a.out[(long long)tid * a.out_stride + col] = __builtin_nan("");
         return;
     }
     int s = kmax == kmin ? 0 : 64 - __clzll((long long)(kmax - kmin));     // bits of (key - base) still open; the same for every rank
@@ -322,7 +314,7 @@ void k_segmented_select(const SelectArgs a)
         const double x = select_value(base[2 * tid]), y = select_value(base[2 * tid + 1]), t = a.t[tid];
         const double d = y - x;
         // numpy.lib._function_base_impl._lerp, as k_percentile_lerp
-        a.out[(long long)tid * a.columns + col] = t >= 0.5 ? y - d * (1.0 - t) : x + d * t;
+        a.out[(long long)tid * a.out_stride + col] = t >= 0.5 ? y - d * (1.0 - t) : x + d * t;
     }
 }
 
@@ -360,6 +352,11 @@ int64_t percentiles_workspace(int64_t n_samples, int64_t n_ensembles, int64_t wa
     return (int64_t)(2 * align256((size_t)items * 8) + align256(temp) + align256((size_t)n_percentiles * 16));
 }
 
+}  // namespace
+
+namespace bisip {
+namespace host {
+
 // numpy's virtual index for method='linear', evaluated as numpy does: its table of methods gives
 // 'linear' the closed form (n - 1) * q, not the general n*q + (alpha + q*(1 - alpha - beta)) - 1
 // (numpy/lib/_function_base_impl.py:_QuantileMethods) -- the two differ in the last bits of the
@@ -379,13 +376,15 @@ int percentile_ranks(long long n, const double *percentiles, int n_percentiles, 
     return BISIP_OK;
 }
 
-// the order statistics of `columns` contiguous columns of n values, SEL_MAX_P percentiles per launch
+// the order statistics of `columns` contiguous columns of n values, SEL_MAX_P percentiles per launch; percentile k
+// of column c goes to d_out[k * out_stride + c] (out_stride 0: columns)
 int select_columns(const double *cols, long long n, long long columns, int n_percentiles, const std::vector<long long> &lo,
-                   const std::vector<double> &t, double *d_out, hipStream_t st)
+                   const std::vector<double> &t, double *d_out, hipStream_t st, long long out_stride)
 {
+    if (out_stride <= 0) out_stride = columns;
     for (int k0 = 0; k0 < n_percentiles; k0 += SEL_MAX_P) {
         SelectArgs sa{};
-        sa.cols = cols; sa.n = n; sa.columns = columns; sa.out = d_out + (long long)k0 * columns;
+        sa.cols = cols; sa.n = n; sa.columns = columns; sa.out = d_out + (long long)k0 * out_stride; sa.out_stride = out_stride;
         sa.n_p = n_percentiles - k0 < SEL_MAX_P ? n_percentiles - k0 : SEL_MAX_P;
         for (int k = 0; k < sa.n_p; ++k) { sa.lo[k] = lo[k0 + k]; sa.t[k] = t[k0 + k]; }
         if (n <= 1024 * 8) hipLaunchKernelGGL(k_segmented_select<8>, dim3((unsigned)columns), dim3(1024), 0, st, sa);
@@ -396,6 +395,24 @@ int select_columns(const double *cols, long long n, long long columns, int n_per
     }
     return BISIP_OK;
 }
+
+// samples (n_samples, E*Wp, ndim) -> cols (n_samples*E*ndim, Wp): one contiguous column of Wp values per (sample,
+// ensemble, parameter), in that order (k_gather_columns_tiled; chain_trace.hip takes its slabs through here)
+int gather_columns_by_sample(const double *d_chain, long long n_samples, long long sample_stride, long long E, long long Wp,
+                             int ndim, double *cols, hipStream_t st)
+{
+    const long long tiles = n_samples * E * ((Wp + 63) / 64) * ((ndim + 63) / 64);
+    if (tiles > 0x7fffffffLL) return fail(BISIP_EUNSUPPORTED, "%lld tiles exceed one grid", tiles);
+    const GatherArgs g{d_chain, n_samples, sample_stride, E, Wp, ndim, cols, 1};
+    hipLaunchKernelGGL(k_gather_columns_tiled, dim3((unsigned)tiles), dim3(256), 0, st, g);
+    HIP_TRY(hipGetLastError());
+    return BISIP_OK;
+}
+
+}  // namespace host
+}  // namespace bisip
+
+namespace {
 
 int percentiles_impl(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
                      int64_t walkers_per_ensemble, int ndim, const double *percentiles, int n_percentiles,

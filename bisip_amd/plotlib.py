@@ -1,16 +1,81 @@
-"""Plots of the shape of a posterior: histograms of every parameter and a corner plot.
+"""Plots of a chain: the walker traces, histograms of every parameter and a corner plot.
 
 The reference draws these with ``ax.hist`` (src/bisip/plotlib.py:56-90) and the ``corner`` package
 (src/bisip/plotlib.py:233-259) from a copy of the chain.  Here both are drawn from counts --
 ``get_param_histogram`` / ``get_corner_histograms`` -- so a chain kept on the GPU (``fit(chain='device')``) is
 counted there and only the counts reach matplotlib, which is imported when a plot is asked for.
+
+``plot_traces`` (src/bisip/plotlib.py:17-54) keeps the reference's figure.  One line per walker is what it draws from a
+chain on the host with few walkers; a chain on the GPU, or a big ensemble, is drawn as a band of per-step percentiles
+over the walkers (``get_trace_percentile``), so that again only the reduced numbers leave the device.
 """
 
 import numpy as np
 
 
 class plotlib(object):
-    """Mixin with the histogram plots (mixed into Inversion)."""
+    """Mixin with the chain plots (mixed into Inversion)."""
+
+    TRACE_LINES_MAX_WALKERS = 128      # style='auto': more walkers than this are drawn as a band
+
+    def plot_traces(self, chain=None, p=(2.5, 50, 97.5), style='auto', **kwargs):
+        """The traces of the MCMC simulation, one axis per parameter over the steps (src/bisip/plotlib.py:17-54).
+
+        ``style='lines'``: one line per walker, ``ax.plot(chain[:, :, i], 'k', alpha=0.3)``, from ``chain (nsteps,
+        nwalkers, ndim)`` or ``get_chain(**kwargs)`` -- the reference's picture.  ``style='band'``: the percentiles ``p``
+        over the walkers at every step from ``get_trace_percentile`` -- the lowest to the highest filled, a line for
+        each one in between (the median in ``'C3'``) -- against the index of the stored sample.  ``style='auto'``: lines
+        for an explicit ``chain`` or a host sampler's chain of at most 128 walkers, else the band.  Returns the figure."""
+        self._check_if_fitted()
+        import matplotlib.pyplot as plt
+        from . import trace as tr
+        if style not in ('auto', 'lines', 'band'):
+            raise ValueError(f"style={style!r}: 'auto', 'lines' or 'band'")
+        if style == 'auto':
+            if chain is not None:
+                lines = np.ndim(chain) == 3
+            else:
+                on_host = not getattr(self._sampler, 'chain_on_device', False)
+                lines = on_host and self.nwalkers <= self.TRACE_LINES_MAX_WALKERS
+            style = 'lines' if lines else 'band'
+        labels = self.param_names
+        fig, axes = plt.subplots(self.param_bounds.shape[1], figsize=(8, 6), sharex=True, squeeze=False)
+        axes = axes[:, 0]
+        if style == 'lines':
+            if chain is None:
+                chain = self.get_chain(**kwargs)
+            elif 'discard' in kwargs or 'thin' in kwargs:
+                raise ValueError('Please pass either a chain obtained with the get_chain() method or pass discard and '
+                                 'thin keywords to parse the full chain. Do not pass both.')
+            chain = np.asarray(chain)
+            if chain.ndim != 3:
+                raise ValueError('A trace needs the unflattened chain (nsteps, nwalkers, ndim); do not pass flat=True.')
+            for i, ax in enumerate(axes):
+                ax.plot(chain[:, :, i], 'k', alpha=0.3)
+            xlim = (0, len(chain))
+        else:
+            pp = np.sort(tr.check_percentiles(p))
+            if pp.size < 1:
+                raise ValueError('a band needs at least one percentile')
+            pct = self.get_trace_percentile(pp, chain=chain, **kwargs)
+            n = pct.shape[1]
+            x = np.arange(n) if chain is not None else tr.used_steps(self._sampler.iteration, kwargs.get('discard', 0),
+                                                                     kwargs.get('thin', 1))
+            inner = range(1, pp.size - 1) if pp.size > 1 else range(1)
+            for i, ax in enumerate(axes):
+                if pp.size > 1:
+                    ax.fill_between(x, pct[0, :, i], pct[-1, :, i], color='k', alpha=0.3, lw=0)
+                for k in inner:
+                    ax.plot(x, pct[k, :, i], c='C3' if pp[k] == 50 else 'k', lw=1)
+            xlim = (x[0], x[-1] + 1) if chain is None else (0, n)
+        for i, ax in enumerate(axes):
+            ax.set_xlim(*xlim)
+            ax.set_ylim(self.param_bounds[:, i])
+            ax.set_ylabel(labels[i])
+            ax.yaxis.set_label_coords(-0.1, 0.5)
+        axes[-1].set_xlabel('Steps')
+        fig.tight_layout()
+        return fig
 
     def plot_histograms(self, chain=None, bins=25, **kwargs):
         """One histogram per parameter, ``bins`` equal bins between the smallest and largest sample, drawn with

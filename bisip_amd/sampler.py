@@ -1535,6 +1535,42 @@ class DeviceEnsembleSampler(_SamplerBase):
         view, edges = self._histogram_edges(bins, range, discard, thin, bounds)
         return device_pair_histograms(view, edges), edges, pair_index(self.ndim)
 
+    def trace_percentiles(self, p=(2.5, 50, 97.5), discard=0, thin=1):
+        """``np.percentile`` over the WALKERS of every ensemble at every sample of ``get_chain(discard, thin)`` -- the
+        trace of the reference's plot_traces (src/bisip/plotlib.py:17-54) as statistics per step -- taken on the device
+        (bisip_chain_trace_dev): from the chain where it lies (``chain_on_device``), else from an upload of the used
+        samples only.  Returns ``(len(p), n, n_ensembles, ndim)``."""
+        from .trace import device_trace
+        return device_trace(self.used_samples_dev(discard, thin), p, mean=False)[0]
+
+    def trace_mean(self, discard=0, thin=1):
+        """The mean over the walkers of every ensemble at every sample of ``get_chain(discard, thin)``, ``(n,
+        n_ensembles, ndim)``, on the device."""
+        from .trace import device_trace
+        return device_trace(self.used_samples_dev(discard, thin), ())[1]
+
+    def log_prob_samples_dev(self, discard=0, thin=1):
+        """``get_log_prob(discard, thin)`` on the device as a ChainView of ``ndim = 1``: the stored log-probabilities
+        themselves with ``chain_on_device``, else an upload of the used ones."""
+        E, Wp, W = self.n_ensembles, self.walkers_per_ensemble, self.nwalkers
+        parts = self._log_prob_parts
+        if parts and all(isinstance(q, _DeviceSlabs) for q in parts):
+            if len(parts) > 1:
+                parts[:] = [_DeviceSlabs(t for q in parts for t in q.tensors)]
+            t = parts[0].tensor()
+            first, n = used_range(t.shape[0], discard, thin)
+            return ChainView(t, n, E, Wp, 1, first * W, int(thin) * W, self.backend)
+        import torch
+        _, n = used_range(self.iteration, discard, thin)
+        used = torch.from_numpy(np.ascontiguousarray(self.get_log_prob(discard=int(discard), thin=int(thin))))
+        return ChainView(used.to(self.backend.device), n, E, Wp, 1, backend=self.backend)
+
+    def log_prob_trace(self, p=(2.5, 50, 97.5), discard=0, thin=1):
+        """``np.percentile`` over the walkers of every ensemble of ``get_log_prob(discard, thin)``, where burn-in shows
+        first: ``(len(p), n, n_ensembles)``, on the device."""
+        from .trace import device_trace
+        return device_trace(self.log_prob_samples_dev(discard, thin), p, mean=False)[0][..., 0]
+
     def _integrating_view(self, log_tau, norm_factor, discard, thin):
         from .decomposition import device_integrating_chain
         view = self.used_samples_dev(discard, thin)

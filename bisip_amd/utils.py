@@ -262,6 +262,67 @@ class utils(object):
             return counts[0], edges[0], pairs
         return hg.host_pair_histograms(self.parse_chain(chain, **kwargs), bins, range, self.param_bounds)
 
+    def _trace_source(self, chain, kwargs):
+        """What a trace is taken from: ``('device', sampler)`` for a fit with the device sampler and no explicit chain,
+        else ``('host', chain (n, W, ndim))`` -- the explicit ``chain`` or ``get_chain(discard, thin)``."""
+        if 'flat' in kwargs:
+            raise TypeError('a trace is taken over the walkers of every step: flat is not accepted')
+        if chain is not None:
+            chain = np.asarray(chain, dtype=np.float64)
+            if chain.ndim != 3:
+                raise ValueError('A trace needs the unflattened chain (nsteps, nwalkers, ndim); do not pass flat=True.')
+            if 'discard' in kwargs or 'thin' in kwargs:
+                raise ValueError('Please pass either a chain obtained with the get_chain() '
+                                 'method or pass discard and thin keywords to parse the full '
+                                 'chain. Do not pass both.')
+            return 'host', chain
+        self._check_if_fitted()
+        extra = set(kwargs) - {'discard', 'thin'}
+        if extra:
+            raise TypeError(f'unexpected keyword(s) {sorted(extra)}')
+        s = self._sampler
+        if getattr(s, 'trace_percentiles', None) is not None:
+            return 'device', s
+        from .chainview import used_range
+        used_range(s.iteration, kwargs.get('discard', 0), kwargs.get('thin', 1))      # ValueError: no samples left
+        return 'host', np.asarray(self.get_chain(**kwargs), dtype=np.float64)
+
+    def get_trace_percentile(self, p=[2.5, 50, 97.5], chain=None, **kwargs):
+        """Percentiles over the WALKERS at every step -- the reference's plot_traces (src/bisip/plotlib.py:17-54) as
+        numbers: ``np.percentile(chain, p, axis=1)`` of ``chain (n, nwalkers, ndim)``, ``(len(p), n, ndim)``, or ``(n,
+        ndim)`` for a scalar ``p``.  ``chain``: an unflattened chain, else ``discard`` / ``thin`` as for ``get_chain``.  A
+        fit with the device sampler is reduced on the GPU (``chain='device'``: where the chain lies), an explicit ``chain``
+        or a host sampler's in NumPy (bisip_amd.trace): the same doubles."""
+        from . import trace as tr
+        pp = tr.check_percentiles(p)
+        kind, src = self._trace_source(chain, kwargs)
+        if kind == 'device':
+            out = src.trace_percentiles(pp, discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1))[:, :, 0, :]
+        else:
+            out = tr.host_trace(src, pp)[0]
+        return out if np.ndim(p) else out[0]
+
+    def get_trace_mean(self, chain=None, **kwargs):
+        """The mean over the walkers at every step, ``(n, ndim)``.  Arguments as get_trace_percentile."""
+        from . import trace as tr
+        kind, src = self._trace_source(chain, kwargs)
+        if kind == 'device':
+            return src.trace_mean(discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1))[:, 0, :]
+        return tr.host_trace(src, ())[1]
+
+    def get_log_prob_trace(self, p=[2.5, 50, 97.5], **kwargs):
+        """Percentiles over the walkers of the stored log-probability at every step, ``(len(p), n)`` (``(n,)`` for a
+        scalar ``p``): where burn-in shows first.  ``discard`` / ``thin`` as for ``get_chain``."""
+        from . import trace as tr
+        pp = tr.check_percentiles(p)
+        kind, src = self._trace_source(None, kwargs)
+        if kind == 'device':
+            out = src.log_prob_trace(pp, discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1))[:, :, 0]
+        else:
+            lp = np.asarray(self._sampler.get_log_prob(discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1)))
+            out = tr.host_trace(lp[:, :, None], pp)[0][:, :, 0]
+        return out if np.ndim(p) else out[0]
+
 
 _QUOTA_APPLIED = False
 

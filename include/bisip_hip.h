@@ -44,7 +44,8 @@ extern "C" {
  *    fp64_stream_probe_dev (+ _lanes), stretch_run_philox_dev (+ stretch_philox_inline) (additions only).
  * 5: chain_autocorr_time_dev (+ _workspace) (additions only).
  * 6: rtd_integrals_dev, rtd_columns_dev (additions only); chain_range_dev, chain_histograms_dev,
- *    chain_pair_histograms_dev came later under the same number (additions only). */
+ *    chain_pair_histograms_dev, then chain_trace_dev (+ _workspace, _lds_walkers) came later under the same number
+ *    (additions only: a caller that needs them looks the symbols up). */
 #define BISIP_ABI_VERSION 6
 
 /* model_id -- the four reference model classes (src/bisip/models.py:182,232,274,308) */
@@ -394,6 +395,31 @@ int bisip_chain_histograms_dev(const double *d_chain, int64_t n_samples, int64_t
 int bisip_chain_pair_histograms_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride,
                                     int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim, const double *d_edges,
                                     int bins, int64_t *d_counts, void *stream);
+
+/* Per-step walker statistics of a chain resident in device memory -- the trace that the reference's plot_traces
+ * (src/bisip/plotlib.py:17-54) draws as one line per walker, reduced along the walker axis: for every used sample s,
+ * ensemble e and parameter q the percentiles and the mean of the walkers_per_ensemble values the ensemble holds at that
+ * sample.  Chain layout, d_chain / sample_stride conventions as for bisip_chain_moments_dev; ndim 1 ... BISIP_MAX_NDIM
+ * (ndim = 1: a stored log-probability tensor (n_samples, walkers)).  percentiles: host array in [0, 100] with 0 ... 8
+ * entries, passed by value (no upload, no wait).
+ *   d_pct (n_percentiles, n_samples, n_ensembles, ndim): np.percentile of the Wp values, the same double -- order
+ *     statistics floor((Wp-1) p/100) and the next, numpy's _lerp (t >= 0.5 ? y - d (1-t) : x + d t); NaN if any of the
+ *     values is NaN.  Not touched when n_percentiles = 0.
+ *   d_mean (n_samples, n_ensembles, ndim) or NULL: their sum in a fixed order (value w goes to partial sum w mod 64, the 64
+ *     partial sums are added pairwise 32, 16, ... 1 apart) divided by Wp.  No floating-point atomics: the same bits on
+ *     every call.  Asking for neither is an error.
+ * Ensembles of up to bisip_chain_trace_lds_walkers(ndim) walkers (the power of two whose padded columns fit the 64 KiB
+ * of LDS a workgroup may allocate statically) are read once and sorted in LDS, one workgroup per (sample, ensemble) or
+ * per group of small ensembles, and need no workspace.  Bigger ones go in slabs of samples through a column-major copy
+ * and the selection kernel of bisip_columns_percentiles_dev: bisip_chain_trace_workspace() BYTES, at most 256 MiB or
+ * one sample of the chain, whichever is larger (0: none needed; < 0: shape not supported).  The results do not depend on
+ * the path.  Asynchronous on stream, no host synchronisation. */
+int64_t bisip_chain_trace_workspace(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim,
+                                    int n_percentiles);
+int bisip_chain_trace_lds_walkers(int ndim);
+int bisip_chain_trace_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+                          int64_t walkers_per_ensemble, int ndim, const double *percentiles, int n_percentiles,
+                          double *d_pct, double *d_mean, void *d_work, int64_t work_bytes, void *stream);
 
 /* np.percentile(rows, p, axis=0) for a device-resident (n_rows, n_cols) array (linear rule):
  * d_out (n_percentiles, n_cols).  Workspace in BYTES (0: more than 2^31 values). */
