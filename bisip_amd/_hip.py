@@ -123,6 +123,10 @@ SYMBOLS = {
     'bisip_chain_trace_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_int, _dp, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_int64, ctypes.c_void_p]),
+    'bisip_chain_rhat_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    'bisip_chain_rhat_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     'bisip_column_percentiles_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     'bisip_column_percentiles_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, _dp, ctypes.c_int,
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
@@ -801,6 +805,23 @@ def chain_trace_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_
                                                 int(walkers_per_ensemble), int(ndim), _p(p) if p.size else None, p.size,
                                                 d_pct_ptr or None, d_mean_ptr or None, d_work_ptr or None,
                                                 int(work_bytes), stream))
+
+
+def chain_rhat_workspace(n_samples, n_ensembles, walkers_per_ensemble, ndim, splits):
+    """Bytes of device scratch chain_rhat_dev needs (0: none; negative: shape not supported)."""
+    return int(load_library().bisip_chain_rhat_workspace(int(n_samples), int(n_ensembles), int(walkers_per_ensemble),
+                                                         int(ndim), int(splits)))
+
+
+def chain_rhat_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, splits, d_mean_ptr,
+                   d_var_ptr, d_rhat_ptr, d_work_ptr=0, work_bytes=0, stream=0):
+    """Mean and variance (ddof = 1) along the step axis of every walker's series, or of its two halves (``splits`` = 1 /
+    2): d_mean, d_var (splits, n_ensembles, walkers_per_ensemble, ndim); and the Gelman-Rubin R-hat over those chains:
+    d_rhat (n_ensembles, ndim).  Each may be 0 / None, not all.  Device pointers (ints), asynchronous on ``stream``."""
+    _check(load_library().bisip_chain_rhat_dev(d_chain_ptr or None, int(n_samples), int(sample_stride), int(n_ensembles),
+                                               int(walkers_per_ensemble), int(ndim), int(splits), d_mean_ptr or None,
+                                               d_var_ptr or None, d_rhat_ptr or None, d_work_ptr or None,
+                                               int(work_bytes), stream))
 
 
 def ensemble_gram_workspace(W, ndim):

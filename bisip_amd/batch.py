@@ -258,6 +258,24 @@ class SpectraBatch:
         out = self._histogram_sampler().log_prob_trace(p, discard=discard, thin=thin)
         return out if np.ndim(p) else out[0]
 
+    def get_rhat(self, discard=0, thin=1, split=True):
+        """The (split) Gelman-Rubin R-hat of every spectrum over its walkers, ``(E, ndim)`` (bisip_amd.convergence) --
+        which fits of a survey to look at, beside the autocorrelation time -- taken on the device for ``chain='device'``
+        and ``'host'`` alike."""
+        return self._histogram_sampler().split_rhat(discard=discard, thin=thin, split=split)
+
+    def get_walker_mean(self, discard=0, thin=1):
+        """The mean of every walker's own series, ``(E, Wp, ndim)``: a stuck walker lies far from its ensemble's."""
+        return self._histogram_sampler().walker_moments(discard=discard, thin=thin)[0]
+
+    def get_walker_std(self, discard=0, thin=1):
+        """The standard deviation (ddof = 1) of every walker's own series, ``(E, Wp, ndim)``."""
+        return np.sqrt(self._histogram_sampler().walker_moments(discard=discard, thin=thin)[1])
+
+    def get_log_prob_rhat(self, discard=0, thin=1, split=True):
+        """R-hat of every spectrum's stored log-probability, ``(E,)``."""
+        return self._histogram_sampler().log_prob_rhat(discard=discard, thin=thin, split=split)
+
     # -- PolynomialDecomposition: relaxation time distribution and integrating parameters ----------------------
     def _decomposition(self):
         if self.model != 'PolynomialDecomposition':

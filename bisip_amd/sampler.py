@@ -1571,6 +1571,27 @@ class DeviceEnsembleSampler(_SamplerBase):
         from .trace import device_trace
         return device_trace(self.log_prob_samples_dev(discard, thin), p, mean=False)[0][..., 0]
 
+    def split_rhat(self, discard=0, thin=1, split=True):
+        """The Gelman-Rubin R-hat of every ensemble over its walkers' series of ``get_chain(discard, thin)``, each cut
+        into halves unless ``split=False`` (bisip_amd.convergence): ``(n_ensembles, ndim)``, taken on the device
+        (bisip_chain_rhat_dev) from the chain where it lies (``chain_on_device``), else from an upload of the used samples
+        only.  A screening number beside the autocorrelation time: walkers of an ensemble are not independent chains."""
+        from .convergence import device_rhat
+        return device_rhat(self.used_samples_dev(discard, thin), split=split)
+
+    def walker_moments(self, discard=0, thin=1):
+        """``(mean, var)`` of every walker's own series of ``get_chain(discard, thin)``, ``(n_ensembles,
+        walkers_per_ensemble, ndim)`` each, the variance with ddof = 1, on the device: a stuck walker is one whose mean
+        lies far from its ensemble's."""
+        from .convergence import device_rhat
+        _, mean, var = device_rhat(self.used_samples_dev(discard, thin), split=False, moments=True)
+        return mean[0], var[0]
+
+    def log_prob_rhat(self, discard=0, thin=1, split=True):
+        """R-hat of every ensemble's stored log-probability, ``(n_ensembles,)``, on the device."""
+        from .convergence import device_rhat
+        return device_rhat(self.log_prob_samples_dev(discard, thin), split=split)[:, 0]
+
     def _integrating_view(self, log_tau, norm_factor, discard, thin):
         from .decomposition import device_integrating_chain
         view = self.used_samples_dev(discard, thin)

@@ -323,6 +323,47 @@ class utils(object):
             out = tr.host_trace(lp[:, :, None], pp)[0][:, :, 0]
         return out if np.ndim(p) else out[0]
 
+    def _walker_moments(self, chain, kwargs):
+        from . import convergence as cv
+        kind, src = self._trace_source(chain, kwargs)
+        if kind == 'device':
+            mean, var = src.walker_moments(discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1))
+            return mean[0], var[0]
+        return cv.walker_moments(src)
+
+    def get_rhat(self, chain=None, split=True, **kwargs):
+        """The Gelman-Rubin potential scale reduction R-hat of every parameter over the walkers, ``(ndim,)``
+        (bisip_amd.convergence): ``sqrt((L - 1) / L + Bn / Wn)`` with ``Wn`` the mean of the walkers' variances and
+        ``Bn`` the variance of their means; ``split=True`` cuts every walker's series into halves first, which also shows
+        drift and works from four used samples up.  Walkers of an ensemble sampler are not independent chains: this is a
+        screening number used beside ``get_autocorr_time``, not a replacement for it.  ``chain``: an unflattened chain,
+        else ``discard`` / ``thin`` as for ``get_chain``.  A fit with the device sampler is reduced on the GPU
+        (``chain='device'``: where the chain lies), an explicit ``chain`` or a host sampler's in NumPy."""
+        from . import convergence as cv
+        kind, src = self._trace_source(chain, kwargs)
+        if kind == 'device':
+            return src.split_rhat(discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1), split=split)[0]
+        return cv.rhat(src, split=split)
+
+    def get_walker_mean(self, chain=None, **kwargs):
+        """The mean of every walker's own series, ``(nwalkers, ndim)``: a walker that never joined the ensemble lies far
+        from the others.  Arguments as get_rhat."""
+        return self._walker_moments(chain, kwargs)[0]
+
+    def get_walker_std(self, chain=None, **kwargs):
+        """The standard deviation of every walker's own series with ddof = 1, ``(nwalkers, ndim)``.  Arguments as
+        get_rhat."""
+        return np.sqrt(self._walker_moments(chain, kwargs)[1])
+
+    def get_log_prob_rhat(self, split=True, **kwargs):
+        """R-hat of the stored log-probability over the walkers, a scalar.  ``discard`` / ``thin`` as for ``get_chain``."""
+        from . import convergence as cv
+        kind, src = self._trace_source(None, kwargs)
+        if kind == 'device':
+            return float(src.log_prob_rhat(discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1), split=split)[0])
+        lp = np.asarray(self._sampler.get_log_prob(discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1)))
+        return float(cv.rhat(lp[:, :, None], split=split)[0])
+
 
 _QUOTA_APPLIED = False
 

@@ -42,11 +42,21 @@ pct = batch.get_param_percentile([16, 50, 84], discard=100)    # (3, E_rank, ndi
 p16, p50, p84 = np.moveaxis(batch.gather(np.moveaxis(pct, 1, 0)), 1, 0)
 band = batch.get_model_percentile([2.5, 50, 97.5], discard=100)         # (3, E_rank, 2, N): the band a fit is plotted with
 accept = batch.gather(batch.acceptance_fraction.mean(axis=1))
+# convergence, where the chain lies: split R-hat per spectrum, and walkers whose own mean lies further from their
+# ensemble's posterior mean than STUCK = 3 of its posterior standard deviations (an example's threshold, nothing more)
+STUCK = 3.0
+rhat = batch.gather(batch.get_rhat(discard=100))               # (E, ndim)
+wmean = batch.get_walker_mean(discard=100)                     # (E_rank, Wp, ndim)
+far = np.abs(wmean - mean[first:last, None, :]) > STUCK * std[first:last, None, :]
+stuck = batch.gather(far.any(axis=2).sum(axis=1))              # (E,) walkers per spectrum
 if rank == 0:
     print('parameters', batch.param_names)
     for e in (0, 1, E - 1):
         print(f'spectrum {e:3d}  mean {np.round(mean[e], 3)}  median {np.round(p50[e], 3)}')
     print('acceptance', round(float(accept.mean()), 3))
+    print(f'{int((rhat.max(axis=1) > 1.05).sum())} of {E} spectra have max split R-hat > 1.05 (a screening number, beside '
+          f'the autocorrelation time); {int(stuck.sum())} of {E * Wp} walkers lie more than {STUCK:g} posterior std from '
+          "their ensemble's mean")
     print('95 % band of Re Z at the lowest frequency, first spectrum of this rank:', np.round(band[[0, 2], 0, 0, -1], 4))
 batch.close()
 if world > 1:

@@ -44,8 +44,8 @@ extern "C" {
  *    fp64_stream_probe_dev (+ _lanes), stretch_run_philox_dev (+ stretch_philox_inline) (additions only).
  * 5: chain_autocorr_time_dev (+ _workspace) (additions only).
  * 6: rtd_integrals_dev, rtd_columns_dev (additions only); chain_range_dev, chain_histograms_dev,
- *    chain_pair_histograms_dev, then chain_trace_dev (+ _workspace, _lds_walkers) came later under the same number
- *    (additions only: a caller that needs them looks the symbols up). */
+ *    chain_pair_histograms_dev, then chain_trace_dev (+ _workspace, _lds_walkers), then chain_rhat_dev (+ _workspace)
+ *    came later under the same number (additions only: a caller that needs them looks the symbols up). */
 #define BISIP_ABI_VERSION 6
 
 /* model_id -- the four reference model classes (src/bisip/models.py:182,232,274,308) */
@@ -420,6 +420,36 @@ int bisip_chain_trace_lds_walkers(int ndim);
 int bisip_chain_trace_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
                           int64_t walkers_per_ensemble, int ndim, const double *percentiles, int n_percentiles,
                           double *d_pct, double *d_mean, void *d_work, int64_t work_bytes, void *stream);
+
+/* Per-walker moments along the STEP axis and the Gelman-Rubin potential scale reduction of a chain resident in device
+ * memory (bisip_amd/convergence.py holds the definitions: walker_moments, gelman_rubin): which ensembles have converged
+ * and which walkers are stuck, without moving the chain.  Walkers of an ensemble sampler are not independent chains:
+ * R-hat here is a screening number beside the autocorrelation time, not a replacement for it.  Chain layout, d_chain /
+ * sample_stride conventions as for bisip_chain_moments_dev; ndim 1 ... BISIP_MAX_NDIM (ndim = 1: a stored
+ * log-probability tensor (n_samples, walkers)).  splits = 1: a chain is a walker's whole series, L = n_samples;
+ * splits = 2: its first and its last L = n_samples / 2 samples are two chains (the middle sample of an odd n_samples is
+ * in neither), which also shows drift.  BISIP_EINVAL when n_samples < 2 * splits or splits * walkers_per_ensemble < 2.
+ *   d_mean, d_var (splits, n_ensembles, walkers_per_ensemble, ndim): mean and variance (ddof = 1) of every chain, from
+ *     sums shifted by the chain's first sample c: d = x - c, S1 += d, S2 += d * d (product rounded on its own), in
+ *     ascending sample order from 0.0; mean = c + S1 / L, var = (S2 - S1 * S1 / L) / (L - 1), 0 where that is negative.
+ *     Short chains of few columns are cut into segments: want = max(1, 262144 / (splits * 256 * ceil(C / 256))), C =
+ *     n_ensembles * walkers_per_ensemble * ndim; seg_len = max(32, ceil(L / want)); segment g sums samples [g * seg_len,
+ *     (g + 1) * seg_len) of the half from 0.0 with the same c, and the segments' sums are added in ascending order.
+ *   d_rhat (n_ensembles, ndim): over the M = splits * walkers_per_ensemble chains c = half * walkers_per_ensemble + w:
+ *     sqrt((L - 1) / L + Bn / Wn), Wn = sum(var) / M, Bn = the variance (ddof = 1) of the means, from sums shifted by the
+ *     mean of chain 0 as above.  Chain c goes to partial sum c mod 64, in turn; the 64 partial sums are added pairwise
+ *     32, 16, ..., 1 apart.  IEEE: NaN when Wn and Bn are 0, inf when only Wn is; a NaN or +-inf in a chain makes its
+ *     variance and the R-hat of that (ensemble, parameter) non-finite and nothing else.
+ * Each of the three may be NULL, not all.  The chain is read once, coalesced.  d_work: bisip_chain_rhat_workspace()
+ * BYTES (0: none needed -- n_ensembles >= 256 with splits * walkers_per_ensemble * ndim <= 4096 and one segment, a
+ * survey; < 0: shape not supported), the segments' sums and the chain moments when the caller does not take them.  The
+ * plan depends on the shape alone, never on the device.  No floating-point atomics: the same bits on every call
+ * (convergence.ordered_rhat gives them in NumPy).  64-bit offsets.  Asynchronous on stream, no host synchronisation. */
+int64_t bisip_chain_rhat_workspace(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim,
+                                   int splits);
+int bisip_chain_rhat_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+                         int64_t walkers_per_ensemble, int ndim, int splits, double *d_mean, double *d_var,
+                         double *d_rhat, void *d_work, int64_t work_bytes, void *stream);
 
 /* np.percentile(rows, p, axis=0) for a device-resident (n_rows, n_cols) array (linear rule):
  * d_out (n_percentiles, n_cols).  Workspace in BYTES (0: more than 2^31 values). */
