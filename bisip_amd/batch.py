@@ -13,7 +13,8 @@ from . import _hip, decomposition
 from .autocorr import AutocorrError
 from .dist import shard_range
 from .sampler import DeviceEnsembleSampler
-from .utils import load_data_batch
+from .summaries import device_model_percentiles
+from .utils import first_if_scalar, load_data_batch
 
 _MODELS = {
     'PolynomialDecomposition': _hip.MODEL_POLYDECOMP,
@@ -150,11 +151,16 @@ class SpectraBatch:
                               'exact log-probability on the final ensembles (tolerance 1e-10)', RuntimeWarning)
         return self
 
-    def _moments(self, discard, thin):
+    def _fitted(self):
+        """The sampler of the fit."""
         if self._sampler is None:
             raise AssertionError('Model is not fitted!')
-        if self._sampler.chain_on_device:
-            return self._sampler.param_moments(discard=discard, thin=thin)
+        return self._sampler
+
+    def _moments(self, discard, thin):
+        s = self._fitted()
+        if s.chain_on_device:
+            return s.param_moments(discard=discard, thin=thin)
         flat = self.get_chain(discard=discard, thin=thin, flat=True)   # (E, n, ndim)
         return flat.mean(axis=1), flat.std(axis=1)
 
@@ -166,10 +172,9 @@ class SpectraBatch:
     def get_param_percentile(self, p=(2.5, 50, 97.5), discard=0, thin=1):
         """Percentiles of every parameter of every spectrum, ``(len(p), E, ndim)`` -- per spectrum
         what the reference's ``get_param_percentile`` returns (src/bisip/utils.py:37-53)."""
-        if self._sampler is None:
-            raise AssertionError('Model is not fitted!')
-        if self._sampler.chain_on_device:
-            return self._sampler.param_percentiles(p, discard=discard, thin=thin)
+        s = self._fitted()
+        if s.chain_on_device:
+            return s.param_percentiles(p, discard=discard, thin=thin)
         flat = self.get_chain(discard=discard, thin=thin, flat=True)   # (E, n, ndim)
         return np.percentile(flat, p, axis=1)
 
@@ -179,32 +184,8 @@ class SpectraBatch:
         band a fit is plotted with.  On the device, many spectra per pass: one forward launch that
         writes the responses column by column, one selection of the order statistics; with
         ``chain='device'`` the chain never leaves HBM."""
-        import torch
-        if self._sampler is None:
-            raise AssertionError('Model is not fitted!')
-        be = self._sampler.backend
-        E, Wp, ndim, N = self.n_spectra, self.nwalkers, self.ndim, self.N
-        p = np.atleast_1d(np.asarray(p, dtype=np.float64))
-        view = self._sampler.used_samples_dev(discard, thin)
-        n = view.n
-        rows_per = n * Wp
-        cols = 2 * N
-        # spectra per pass: the responses of a pass stay under decomposition.RTD_PASS_BYTES
-        G = int(min(E, max(1, decomposition.RTD_PASS_BYTES // (rows_per * cols * 8))))
-        out = np.empty((p.size, E, cols))
-        grid = view.samples().reshape(n, E, Wp, ndim)
-        for g0 in range(0, E, G):
-            g1 = min(E, g0 + G)
-            k = g1 - g0
-            rows = grid[:, g0:g1].permute(1, 0, 2, 3).reshape(k, rows_per, ndim)   # one copy: spectrum-major
-            Zc = be.empty((k, cols, rows_per), torch.float64)                      # one column per (spectrum, part, frequency)
-            self.ctx.forward_columns_dev(g0, k, rows.data_ptr(), k * rows_per, Zc.data_ptr(), be.stream())
-            res = be.empty((p.size, k * cols), torch.float64)
-            _hip.columns_percentiles_dev(Zc.data_ptr(), k * cols, rows_per, p, res.data_ptr(), be.stream())
-            be.synchronize()
-            out[:, g0:g1] = res.cpu().numpy().reshape(p.size, k, cols)
-            del rows, Zc, res
-        return out.reshape(p.size, E, 2, N)
+        out = device_model_percentiles(self._fitted().used_samples_dev(discard, thin), self.ctx, p)
+        return out.reshape(-1, self.n_spectra, 2, self.N)
 
     def get_autocorr_time(self, discard=0, thin=1, c=5, tol=50, quiet=False):
         """emcee's integrated autocorrelation time of every parameter of every spectrum, ``(E, ndim)``, in
@@ -212,18 +193,11 @@ class SpectraBatch:
         the device for ``chain='device'`` and ``'host'`` alike.  Raises AutocorrError when the chain is shorter
         than ``tol`` times an estimate (``quiet``: warns).  A multi-GPU survey joins the ranks' blocks with
         ``gather(get_autocorr_time(...))``."""
-        if self._sampler is None:
-            raise AssertionError('Model is not fitted!')
         try:
-            tau = self._sampler.get_autocorr_time(discard=discard, thin=thin, c=c, tol=tol, quiet=quiet)
+            tau = self._fitted().get_autocorr_time(discard=discard, thin=thin, c=c, tol=tol, quiet=quiet)
         except AutocorrError as err:
             raise AutocorrError(np.reshape(err.tau, (self.n_spectra, self.ndim)), *err.args) from None
         return np.reshape(tau, (self.n_spectra, self.ndim))
-
-    def _histogram_sampler(self):
-        if self._sampler is None:
-            raise AssertionError('Model is not fitted!')
-        return self._sampler
 
     def get_param_histogram(self, bins=25, range=None, discard=0, thin=1):
         """``np.histogram`` of every parameter of every spectrum, ``(counts (E, ndim, bins) int64, edges (E, ndim,
@@ -231,50 +205,46 @@ class SpectraBatch:
         counted on the device for ``chain='device'`` and ``'host'`` alike.  ``range``: None (each spectrum's own min
         and max), 'bounds' (the prior box: the same edges for every spectrum) or an array ``(ndim, 2)`` / ``(E, ndim,
         2)``."""
-        return self._histogram_sampler().param_histograms(bins, range, discard=discard, thin=thin,
-                                                          bounds=self.param_bounds)
+        return self._fitted().param_histograms(bins, range, discard=discard, thin=thin, bounds=self.param_bounds)
 
     def get_corner_histograms(self, bins=20, range=None, discard=0, thin=1):
         """``np.histogram2d`` of every pair of parameters of every spectrum, ``(counts (E, npairs, bins, bins) int64,
         edges (E, ndim, bins + 1), pairs)`` with ``pairs = np.triu_indices(ndim, 1)`` -- per spectrum the panels of
         the reference's plot_corner (src/bisip/plotlib.py:233-259)."""
-        return self._histogram_sampler().pair_histograms(bins, range, discard=discard, thin=thin,
-                                                         bounds=self.param_bounds)
+        return self._fitted().pair_histograms(bins, range, discard=discard, thin=thin, bounds=self.param_bounds)
 
     def get_trace_percentile(self, p=(2.5, 50, 97.5), discard=0, thin=1):
         """Percentiles over the WALKERS of every spectrum at every step, ``(len(p), n, E, ndim)`` (``(n, E, ndim)`` for a
         scalar ``p``) -- per spectrum the trace of the reference's plot_traces (src/bisip/plotlib.py:17-54) as numbers --
         taken on the device for ``chain='device'`` and ``'host'`` alike."""
-        out = self._histogram_sampler().trace_percentiles(p, discard=discard, thin=thin)
-        return out if np.ndim(p) else out[0]
+        return first_if_scalar(p, self._fitted().trace_percentiles(p, discard=discard, thin=thin))
 
     def get_trace_mean(self, discard=0, thin=1):
         """The mean over the walkers of every spectrum at every step, ``(n, E, ndim)``."""
-        return self._histogram_sampler().trace_mean(discard=discard, thin=thin)
+        return self._fitted().trace_mean(discard=discard, thin=thin)
 
     def get_log_prob_trace(self, p=(2.5, 50, 97.5), discard=0, thin=1):
         """Percentiles over the walkers of every spectrum's stored log-probability at every step, ``(len(p), n, E)``
         (``(n, E)`` for a scalar ``p``): where burn-in shows first."""
-        out = self._histogram_sampler().log_prob_trace(p, discard=discard, thin=thin)
-        return out if np.ndim(p) else out[0]
+        return first_if_scalar(p, self._fitted().log_prob_trace(p, discard=discard, thin=thin))
 
     def get_rhat(self, discard=0, thin=1, split=True):
         """The (split) Gelman-Rubin R-hat of every spectrum over its walkers, ``(E, ndim)`` (bisip_amd.convergence) --
         which fits of a survey to look at, beside the autocorrelation time -- taken on the device for ``chain='device'``
         and ``'host'`` alike."""
-        return self._histogram_sampler().split_rhat(discard=discard, thin=thin, split=split)
+        return self._fitted().split_rhat(discard=discard, thin=thin, split=split)
 
     def get_walker_mean(self, discard=0, thin=1):
         """The mean of every walker's own series, ``(E, Wp, ndim)``: a stuck walker lies far from its ensemble's."""
-        return self._histogram_sampler().walker_moments(discard=discard, thin=thin)[0]
+        return self._fitted().walker_moments(discard=discard, thin=thin)[0]
 
     def get_walker_std(self, discard=0, thin=1):
         """The standard deviation (ddof = 1) of every walker's own series, ``(E, Wp, ndim)``."""
-        return np.sqrt(self._histogram_sampler().walker_moments(discard=discard, thin=thin)[1])
+        return np.sqrt(self._fitted().walker_moments(discard=discard, thin=thin)[1])
 
     def get_log_prob_rhat(self, discard=0, thin=1, split=True):
         """R-hat of every spectrum's stored log-probability, ``(E,)``."""
-        return self._histogram_sampler().log_prob_rhat(discard=discard, thin=thin, split=split)
+        return self._fitted().log_prob_rhat(discard=discard, thin=thin, split=split)
 
     # -- PolynomialDecomposition: relaxation time distribution and integrating parameters ----------------------
     def _decomposition(self):
@@ -283,9 +253,7 @@ class SpectraBatch:
 
     def _decomposition_sampler(self):
         self._decomposition()
-        if self._sampler is None:
-            raise AssertionError('Model is not fitted!')
-        return self._sampler
+        return self._fitted()
 
     def rtd(self, theta):
         """The RTD ``m_l = sum_p a_p * log_tau_l**p`` of theta ``(E, n, ndim)`` on ``log_tau`` (host): ``(E, n, L)``."""
@@ -304,8 +272,7 @@ class SpectraBatch:
     def get_integrating_chain(self, discard=0, thin=1, flat=False):
         """``(m_total, log_tau_mean, m_norm)`` of every sample of every spectrum, computed on the GPU:
         ``(n', E, Wp, 3)`` as get_chain, ``(E, n' * Wp, 3)`` with ``flat``."""
-        s = self._decomposition_sampler()
-        d = s.integrating_chain_dev(self.log_tau, self.norm_factor, discard=discard, thin=thin)
+        d = self._decomposition_sampler().integrating_chain_dev(self.log_tau, self.norm_factor, discard, thin)
         ch = d.cpu().numpy().reshape(-1, self.n_spectra, self.nwalkers, 3)
         if flat:
             ch = ch.transpose(1, 0, 2, 3).reshape(self.n_spectra, -1, 3)
@@ -323,13 +290,12 @@ class SpectraBatch:
         """Percentiles of ``(m_total, log_tau_mean, m_norm)`` per spectrum, ``(len(p), E, 3)`` (``(E, 3)`` for a
         scalar ``p``).  A multi-GPU survey joins the ranks with ``gather(np.moveaxis(pct, 1, 0))``."""
         out = self._decomposition_sampler().integrating_percentiles(p, self.log_tau, self.norm_factor, discard, thin)
-        return out if np.ndim(p) else out[0]
+        return first_if_scalar(p, out)
 
     def get_rtd_percentile(self, p=(2.5, 50, 97.5), discard=0, thin=1):
         """Percentiles of the RTD ``m_l`` per spectrum, ``(len(p), E, L)`` (``(E, L)`` for a scalar ``p``): the m_l
         go column by column on the device, spectra in passes under ``decomposition.RTD_PASS_BYTES``."""
-        out = self._decomposition_sampler().rtd_percentiles(p, self.log_tau, discard, thin)
-        return out if np.ndim(p) else out[0]
+        return first_if_scalar(p, self._decomposition_sampler().rtd_percentiles(p, self.log_tau, discard, thin))
 
     def get_param_std(self, discard=0, thin=1):
         """Posterior standard deviation, ``(E, ndim)`` (src/bisip/utils.py:71-85)."""
@@ -337,25 +303,19 @@ class SpectraBatch:
 
     def get_chain(self, discard=0, thin=1, flat=False):
         """(nsteps', E, Wp, ndim); flat=True -> (E, nsteps'*Wp, ndim)."""
-        if self._sampler is None:
-            raise AssertionError('Model is not fitted!')
-        ch = self._sampler.get_chain(discard=discard, thin=thin)
+        ch = self._fitted().get_chain(discard=discard, thin=thin)
         ch = ch.reshape(ch.shape[0], self.n_spectra, self.nwalkers, self.ndim)
         if flat:
             ch = ch.transpose(1, 0, 2, 3).reshape(self.n_spectra, -1, self.ndim)
         return ch
 
     def get_log_prob(self, discard=0, thin=1):
-        if self._sampler is None:
-            raise AssertionError('Model is not fitted!')
-        lp = self._sampler.get_log_prob(discard=discard, thin=thin)
+        lp = self._fitted().get_log_prob(discard=discard, thin=thin)
         return lp.reshape(lp.shape[0], self.n_spectra, self.nwalkers)
 
     @property
     def acceptance_fraction(self):
-        if self._sampler is None:
-            raise AssertionError('Model is not fitted!')
-        return self._sampler.acceptance_fraction.reshape(self.n_spectra, self.nwalkers)
+        return self._fitted().acceptance_fraction.reshape(self.n_spectra, self.nwalkers)
 
     def gather(self, per_spectrum, group=None):
         """The end of a multi-GPU survey: every rank passes a per-spectrum result of ITS block --

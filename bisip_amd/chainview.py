@@ -1,10 +1,10 @@
 """The used samples of a chain on the device, as every posterior summary takes them.
 
 ``used_range`` is emcee's discard / thin arithmetic.  A ``ChainView`` says where the used samples lie in a float64
-device tensor and carries the stream and allocator the summary works with.  ``device_moments`` and
-``device_percentiles`` are the two summaries that any view has (bisip_chain_moments_dev,
-bisip_chain_percentiles_dev); the others are in bisip_amd.autocorr, bisip_amd.histogram and
-bisip_amd.decomposition.
+device tensor and carries the stream and allocator the summary works with.  ``_DeviceSlabs`` is how a device sampler
+keeps the stored samples of a run there (bisip_amd.sampler writes them, bisip_amd.summaries views them).
+``device_moments`` and ``device_percentiles`` are the two summaries that any view has (bisip_chain_moments_dev,
+bisip_chain_percentiles_dev); the others are in bisip_amd.autocorr, bisip_amd.histogram and bisip_amd.decomposition.
 """
 
 import numpy as np
@@ -97,6 +97,40 @@ class ChainView:
         t = self.tensor
         return torch.as_strided(t, (self.n, self.n_ensembles * self.walkers_per_ensemble, self.ndim),
                                 (self.stride, self.ndim, 1), t.storage_offset() + self.offset)
+
+
+class _DeviceSlabs:
+    """Stored samples that stay in device memory (one torch tensor per chunk).  Behaves like a chain part for the
+    bookkeeping (``shape``) and becomes a host array the first time the host asks for it."""
+
+    def __init__(self, tensors):
+        self.tensors = list(tensors)
+
+    @property
+    def shape(self):
+        return (sum(int(t.shape[0]) for t in self.tensors),) + tuple(self.tensors[0].shape[1:])
+
+    def tensor(self):
+        if len(self.tensors) > 1:
+            import torch
+            self.tensors = [torch.cat(self.tensors, dim=0)]
+        return self.tensors[0]
+
+    def materialize(self):
+        """Host copy, made once; the samples also stay on the device for the summaries."""
+        if getattr(self, '_host', None) is None:
+            self._host = self.tensor().cpu().numpy()
+        return self._host
+
+
+def _merge_device_parts(parts):
+    """True when the parts of a stored chain (one per run) all lie on the device; they then become ONE part, merged
+    where they lie.  False, and nothing changes, when there are none or some are host arrays."""
+    if not parts or not all(isinstance(p, _DeviceSlabs) for p in parts):
+        return False
+    if len(parts) > 1:
+        parts[:] = [_DeviceSlabs(t for p in parts for t in p.tensors)]
+    return True
 
 
 def device_moments(view):

@@ -394,9 +394,9 @@ class PolynomialDecomposition(Inversion):
         ndim = len(self.params)
         s = self._device_chain_sampler(chain, kwargs)
         if s is not None:
-            return s.used_samples_dev(kwargs.get('discard', 0), kwargs.get('thin', 1))
+            return s.used_samples_dev(**_utils.discard_thin(kwargs))
         if chain is None:
-            used_range(self.sampler.iteration, kwargs.get('discard', 0), kwargs.get('thin', 1))
+            used_range(self.sampler.iteration, **_utils.discard_thin(kwargs))
         chain = chain if chain is None else np.asarray(chain, dtype=np.float64)
         flat = np.ascontiguousarray(self.parse_chain(chain, **dict(kwargs)), dtype=np.float64)
         if flat.ndim != 2 or flat.shape[1] != ndim:
@@ -430,14 +430,13 @@ class PolynomialDecomposition(Inversion):
 
     def get_integrating_percentile(self, p=[2.5, 50, 97.5], chain=None, **kwargs):
         """Percentiles of ``(m_total, log_tau_mean, m_norm)``: ``(len(p), 3)``, ``(3,)`` for a scalar ``p``."""
-        out = device_percentiles(self._integrating_view(chain, kwargs), p)[:, 0, :]
-        return out if np.ndim(p) else out[0]
+        return _utils.first_if_scalar(p, device_percentiles(self._integrating_view(chain, kwargs), p)[:, 0, :])
 
     def get_rtd_percentile(self, p=[2.5, 50, 97.5], chain=None, **kwargs):
         """Percentiles of the RTD ``m_l`` over the chain -- the band of the tutorial's RTD plot: ``(len(p), L)``,
         ``(L,)`` for a scalar ``p``."""
         out = _decomp.device_rtd_percentiles(self._decomposition_samples(chain, kwargs), p, self.log_tau)[:, 0, :]
-        return out if np.ndim(p) else out[0]
+        return _utils.first_if_scalar(p, out)
 
 
 class PeltonColeCole(Inversion):

@@ -12,6 +12,8 @@ over the walkers (``get_trace_percentile``), so that again only the reduced numb
 
 import numpy as np
 
+from .utils import discard_thin, refuse_discard_of_a_chain
+
 
 class plotlib(object):
     """Mixin with the chain plots (mixed into Inversion)."""
@@ -44,9 +46,8 @@ class plotlib(object):
         if style == 'lines':
             if chain is None:
                 chain = self.get_chain(**kwargs)
-            elif 'discard' in kwargs or 'thin' in kwargs:
-                raise ValueError('Please pass either a chain obtained with the get_chain() method or pass discard and '
-                                 'thin keywords to parse the full chain. Do not pass both.')
+            else:
+                refuse_discard_of_a_chain(kwargs)
             chain = np.asarray(chain)
             if chain.ndim != 3:
                 raise ValueError('A trace needs the unflattened chain (nsteps, nwalkers, ndim); do not pass flat=True.')
@@ -59,8 +60,7 @@ class plotlib(object):
                 raise ValueError('a band needs at least one percentile')
             pct = self.get_trace_percentile(pp, chain=chain, **kwargs)
             n = pct.shape[1]
-            x = np.arange(n) if chain is not None else tr.used_steps(self._sampler.iteration, kwargs.get('discard', 0),
-                                                                     kwargs.get('thin', 1))
+            x = np.arange(n) if chain is not None else tr.used_steps(self._sampler.iteration, **discard_thin(kwargs))
             inner = range(1, pp.size - 1) if pp.size > 1 else range(1)
             for i, ax in enumerate(axes):
                 if pp.size > 1:

@@ -40,8 +40,9 @@ import os
 
 import numpy as np
 
-from .chainview import ChainView, device_moments, device_percentiles, used_range
+from .chainview import _DeviceSlabs, _merge_device_parts
 from .dist import all_gather_rows, shard_range
+from .summaries import DeviceChainSummaries
 
 
 class _one_blas_thread(object):
@@ -233,37 +234,11 @@ def affine_splits(seed, nwalkers, step0, nsteps):
     return out
 
 
-class _DeviceSlabs:
-    """Stored samples that stay in device memory (one torch tensor per chunk).  Behaves like
-    a chain part for the bookkeeping (``shape``) and becomes a host array the first time the
-    host asks for it."""
-
-    def __init__(self, tensors):
-        self.tensors = list(tensors)
-
-    @property
-    def shape(self):
-        return (sum(int(t.shape[0]) for t in self.tensors),) + tuple(self.tensors[0].shape[1:])
-
-    def tensor(self):
-        if len(self.tensors) > 1:
-            import torch
-            self.tensors = [torch.cat(self.tensors, dim=0)]
-        return self.tensors[0]
-
-    def materialize(self):
-        """Host copy, made once; the samples also stay on the device for the summaries."""
-        if getattr(self, '_host', None) is None:
-            self._host = self.tensor().cpu().numpy()
-        return self._host
-
-
 def _host_parts(parts):
     """Chain parts as host arrays.  Device-resident parts are first merged into one (on the
     device) and stay what they are: get_chain() must not take the chain away from
     param_moments() / param_percentiles()."""
-    if len(parts) > 1 and all(isinstance(p, _DeviceSlabs) for p in parts):
-        parts[:] = [_DeviceSlabs(t for p in parts for t in p.tensors)]
+    _merge_device_parts(parts)
     return [p.materialize() if isinstance(p, _DeviceSlabs) else p for p in parts]
 
 
@@ -828,13 +803,14 @@ class HipStretchBackend:
         self.torch.cuda.synchronize(self.device)
 
 
-class DeviceEnsembleSampler(_SamplerBase):
+class DeviceEnsembleSampler(DeviceChainSummaries, _SamplerBase):
     """Stretch-move sampler whose ensemble, chain and half-step arithmetic live on the GPU.
 
     Same interface, RNG contract and chain as ``EnsembleSampler``.  ``ctx`` is a
     ``bisip_amd._hip.HipContext``; ``backend`` is injectable so the multi-rank driver
     logic can be exercised on CPU (tests/test_dist.py).
     ``chunk`` bounds the number of steps whose RNG stream / chain slab are resident at once.
+    The posterior summaries of the stored chain are ``DeviceChainSummaries`` (bisip_amd.summaries).
 
     **No chunk is kept that a failing tier produced.**  PolynomialDecomposition samples with a QR-reduced
     kernel that BISIP_VARIANT_AUTO chose from an error estimate on probe rows.  The launches here hand over
@@ -1443,197 +1419,3 @@ class DeviceEnsembleSampler(_SamplerBase):
         if self._coords.nbytes >= (8 << 20):      # a big ensemble: the arrays returned are the sampler's own host copy
             return self._coords, self._lp         # of its last state (another 56 MB copy at a million walkers: 5 ms)
         return self._coords.copy(), self._lp.copy()
-
-    # -- summaries of a device-resident chain -------------------------------------------
-    def device_chain(self):
-        """All stored samples as ONE torch tensor (iteration, W, ndim) on the device
-        (``chain_on_device=True`` runs only)."""
-        parts = self._chain_parts
-        if not parts or not all(isinstance(p, _DeviceSlabs) for p in parts):
-            raise AttributeError('the chain is not resident on the device '
-                                 '(run with chain_on_device=True)')
-        if len(parts) > 1:
-            parts[:] = [_DeviceSlabs(t for p in parts for t in p.tensors)]
-        return parts[0].tensor()
-
-    def used_samples_dev(self, discard=0, thin=1, upload=True):
-        """``get_chain(discard, thin)`` on the device as a ChainView (bisip_amd.chainview): the stored chain itself
-        with ``chain_on_device``, else an upload of the used samples only -- or, with ``upload=False``,
-        device_chain()'s AttributeError."""
-        E, Wp, W, ndim = self.n_ensembles, self.walkers_per_ensemble, self.nwalkers, self.ndim
-        if self.chain_on_device or not upload:
-            t = self.device_chain()
-            first, n = used_range(t.shape[0], discard, thin)
-            return ChainView(t, n, E, Wp, ndim, first * W * ndim, int(thin) * W * ndim, self.backend)
-        import torch
-        _, n = used_range(self.iteration, discard, thin)
-        used = torch.from_numpy(np.ascontiguousarray(self.get_chain(discard=int(discard), thin=int(thin))))
-        return ChainView(used.to(self.backend.device), n, E, Wp, ndim, backend=self.backend)
-
-    def param_moments(self, discard=0, thin=1):
-        """Mean and standard deviation of every parameter over the used samples, flattened over the walkers of each
-        ensemble -- ``np.mean`` / ``np.std`` of ``get_chain(discard, thin, flat=True)`` (reference:
-        src/bisip/utils.py:55-85) -- computed on the device, only the two
-        ``(n_ensembles, ndim)`` results come back.  Returns ``(mean, std)``."""
-        return device_moments(self.used_samples_dev(discard, thin, upload=False))
-
-    def param_percentiles(self, p=(2.5, 50, 97.5), discard=0, thin=1):
-        """``np.percentile(get_chain(discard, thin, flat=True), p, axis=0)`` per ensemble
-        (reference: src/bisip/utils.py:37-53), sorted and interpolated on the device; returns
-        ``(len(p), n_ensembles, ndim)``."""
-        return device_percentiles(self.used_samples_dev(discard, thin, upload=False), p)
-
-    def get_autocorr_time(self, discard=0, thin=1, c=5, tol=50, quiet=False):
-        """emcee's integrated autocorrelation time of ``get_chain(discard, thin)``, times ``thin``, every
-        (ensemble, parameter) estimated on the device (bisip_chain_autocorr_time_dev): from the chain where it
-        lies (``chain_on_device``), else from an upload of the used samples only.  ``(ndim,)`` for one ensemble,
-        ``(n_ensembles, ndim)`` for a batch.  The ``tol`` test is that of integrated_time, per ensemble (every
-        ensemble has the same number of samples); the AutocorrError carries every estimate."""
-        from .autocorr import check_c, check_tol, device_integrated_time
-        c = check_c(c)
-        view = self.used_samples_dev(discard, thin)
-        tau, _ = device_integrated_time(view, c)
-        E = self.n_ensembles
-        what = 'parameter(s)' if E == 1 else f'(ensemble, parameter) pair(s) of {E} ensembles'
-        tau = check_tol(tau if E > 1 else tau[0], view.n, tol, quiet, what)
-        return int(thin) * tau
-
-    def param_range(self, discard=0, thin=1):
-        """Min and max of the finite values of every parameter over ``get_chain(discard, thin)`` per ensemble,
-        ``(n_ensembles, ndim, 2)``, and how many of its values are not finite, ``(n_ensembles, ndim)``, taken on the
-        device (bisip_chain_range_dev)."""
-        from .histogram import device_param_range
-        return device_param_range(self.used_samples_dev(discard, thin))
-
-    def _histogram_edges(self, bins, range, discard, thin, bounds):
-        """The used samples on the device (a ChainView) and the edges ``(n_ensembles, ndim, bins + 1)`` of a
-        ``range`` argument (None, 'bounds' or an array: bisip_amd.histogram)."""
-        from . import histogram as hg
-        bins = hg.check_bins(bins)
-        view = self.used_samples_dev(discard, thin)
-        r = hg.resolve_range(range, view.n_ensembles, view.ndim, bounds, lambda: hg.device_param_range(view))
-        return view, hg.edges_from_range(r, bins)
-
-    def param_histograms(self, bins=25, range=None, discard=0, thin=1, bounds=None):
-        """``np.histogram`` of every parameter of every ensemble over ``get_chain(discard, thin, flat=True)`` -- the
-        counts of the reference's plot_histograms (src/bisip/plotlib.py:56-90) -- counted on the device
-        (bisip_chain_histograms_dev): from the chain where it lies (``chain_on_device``), else from an upload of the
-        used samples only.  ``range``: None (min and max of the samples), 'bounds' (the prior box ``bounds (2, ndim)``)
-        or an array ``(ndim, 2)`` / ``(n_ensembles, ndim, 2)``.  Returns ``(counts (n_ensembles, ndim, bins) int64, edges
-        (n_ensembles, ndim, bins + 1))``."""
-        from .histogram import device_histograms
-        view, edges = self._histogram_edges(bins, range, discard, thin, bounds)
-        return device_histograms(view, edges), edges
-
-    def pair_histograms(self, bins=20, range=None, discard=0, thin=1, bounds=None):
-        """``np.histogram2d`` of every pair of parameters of every ensemble -- the panels of the reference's
-        plot_corner (src/bisip/plotlib.py:233-259) -- counted on the device (bisip_chain_pair_histograms_dev).
-        Returns ``(counts (n_ensembles, npairs, bins, bins) int64, edges (n_ensembles, ndim, bins + 1), pairs)``,
-        ``pairs = np.triu_indices(ndim, 1)``; ``counts[e, q, a, b]``: parameter ``pairs[0][q]`` in bin ``a``,
-        ``pairs[1][q]`` in bin ``b``."""
-        from .histogram import device_pair_histograms, pair_index
-        view, edges = self._histogram_edges(bins, range, discard, thin, bounds)
-        return device_pair_histograms(view, edges), edges, pair_index(self.ndim)
-
-    def trace_percentiles(self, p=(2.5, 50, 97.5), discard=0, thin=1):
-        """``np.percentile`` over the WALKERS of every ensemble at every sample of ``get_chain(discard, thin)`` -- the
-        trace of the reference's plot_traces (src/bisip/plotlib.py:17-54) as statistics per step -- taken on the device
-        (bisip_chain_trace_dev): from the chain where it lies (``chain_on_device``), else from an upload of the used
-        samples only.  Returns ``(len(p), n, n_ensembles, ndim)``."""
-        from .trace import device_trace
-        return device_trace(self.used_samples_dev(discard, thin), p, mean=False)[0]
-
-    def trace_mean(self, discard=0, thin=1):
-        """The mean over the walkers of every ensemble at every sample of ``get_chain(discard, thin)``, ``(n,
-        n_ensembles, ndim)``, on the device."""
-        from .trace import device_trace
-        return device_trace(self.used_samples_dev(discard, thin), ())[1]
-
-    def log_prob_samples_dev(self, discard=0, thin=1):
-        """``get_log_prob(discard, thin)`` on the device as a ChainView of ``ndim = 1``: the stored log-probabilities
-        themselves with ``chain_on_device``, else an upload of the used ones."""
-        E, Wp, W = self.n_ensembles, self.walkers_per_ensemble, self.nwalkers
-        parts = self._log_prob_parts
-        if parts and all(isinstance(q, _DeviceSlabs) for q in parts):
-            if len(parts) > 1:
-                parts[:] = [_DeviceSlabs(t for q in parts for t in q.tensors)]
-            t = parts[0].tensor()
-            first, n = used_range(t.shape[0], discard, thin)
-            return ChainView(t, n, E, Wp, 1, first * W, int(thin) * W, self.backend)
-        import torch
-        _, n = used_range(self.iteration, discard, thin)
-        used = torch.from_numpy(np.ascontiguousarray(self.get_log_prob(discard=int(discard), thin=int(thin))))
-        return ChainView(used.to(self.backend.device), n, E, Wp, 1, backend=self.backend)
-
-    def log_prob_trace(self, p=(2.5, 50, 97.5), discard=0, thin=1):
-        """``np.percentile`` over the walkers of every ensemble of ``get_log_prob(discard, thin)``, where burn-in shows
-        first: ``(len(p), n, n_ensembles)``, on the device."""
-        from .trace import device_trace
-        return device_trace(self.log_prob_samples_dev(discard, thin), p, mean=False)[0][..., 0]
-
-    def split_rhat(self, discard=0, thin=1, split=True):
-        """The Gelman-Rubin R-hat of every ensemble over its walkers' series of ``get_chain(discard, thin)``, each cut
-        into halves unless ``split=False`` (bisip_amd.convergence): ``(n_ensembles, ndim)``, taken on the device
-        (bisip_chain_rhat_dev) from the chain where it lies (``chain_on_device``), else from an upload of the used samples
-        only.  A screening number beside the autocorrelation time: walkers of an ensemble are not independent chains."""
-        from .convergence import device_rhat
-        return device_rhat(self.used_samples_dev(discard, thin), split=split)
-
-    def walker_moments(self, discard=0, thin=1):
-        """``(mean, var)`` of every walker's own series of ``get_chain(discard, thin)``, ``(n_ensembles,
-        walkers_per_ensemble, ndim)`` each, the variance with ddof = 1, on the device: a stuck walker is one whose mean
-        lies far from its ensemble's."""
-        from .convergence import device_rhat
-        _, mean, var = device_rhat(self.used_samples_dev(discard, thin), split=False, moments=True)
-        return mean[0], var[0]
-
-    def log_prob_rhat(self, discard=0, thin=1, split=True):
-        """R-hat of every ensemble's stored log-probability, ``(n_ensembles,)``, on the device."""
-        from .convergence import device_rhat
-        return device_rhat(self.log_prob_samples_dev(discard, thin), split=split)[:, 0]
-
-    def _integrating_view(self, log_tau, norm_factor, discard, thin):
-        from .decomposition import device_integrating_chain
-        view = self.used_samples_dev(discard, thin)
-        return view.derived(device_integrating_chain(view, log_tau, norm_factor))
-
-    def integrating_chain_dev(self, log_tau, norm_factor, discard=0, thin=1):
-        """PolynomialDecomposition's ``(m_total, log_tau_mean, m_norm)`` of every sample of ``get_chain(discard,
-        thin)`` (bisip_rtd_integrals_dev; bisip_amd.decomposition): a device tensor ``(n, nwalkers, 3)``.
-        ``norm_factor``: scalar or one per ensemble."""
-        return self._integrating_view(log_tau, norm_factor, discard, thin).tensor
-
-    def integrating_moments(self, log_tau, norm_factor, discard=0, thin=1):
-        """Mean and std of the integrating parameters per ensemble, ``(n_ensembles, 3)`` each, on the device."""
-        return device_moments(self._integrating_view(log_tau, norm_factor, discard, thin))
-
-    def integrating_percentiles(self, p, log_tau, norm_factor, discard=0, thin=1):
-        """np.percentile of the integrating parameters per ensemble, ``(len(p), n_ensembles, 3)``, on the device."""
-        return device_percentiles(self._integrating_view(log_tau, norm_factor, discard, thin), p)
-
-    def rtd_percentiles(self, p, log_tau, discard=0, thin=1):
-        """np.percentile of the RTD ``m_l`` per ensemble, ``(len(p), n_ensembles, L)``, on the device
-        (bisip_rtd_columns_dev, then the selection of bisip_columns_percentiles_dev)."""
-        from .decomposition import device_rtd_percentiles
-        return device_rtd_percentiles(self.used_samples_dev(discard, thin), p, log_tau)
-
-    def model_percentiles(self, p=(2.5, 50, 97.5), discard=0, thin=1):
-        """``np.percentile(forward(get_chain(discard, thin, flat=True)), p, axis=0)`` -- the
-        reference's get_model_percentile (src/bisip/utils.py:17-35) -- without the chain leaving
-        the device: batched forward over the stored samples, written column by column, then the
-        selection of the order statistics from each column.  One ensemble only (NotImplementedError
-        otherwise); returns ``(len(p), 2, N)``."""
-        import torch
-        from . import _hip
-        if self.n_ensembles != 1:
-            raise NotImplementedError('model percentiles of a batch of spectra: one spectrum at a time')
-        rows = self.used_samples_dev(discard, thin, upload=False).samples().reshape(-1, self.ndim).contiguous()
-        be, ctx = self.backend, self.backend.ctx
-        p = np.atleast_1d(np.asarray(p, dtype=np.float64))
-        n, cols = int(rows.shape[0]), 2 * ctx.N
-        Zc = be.empty((cols, n), torch.float64)                  # the responses, one column per (part, frequency)
-        ctx.forward_columns_dev(0, 1, rows.data_ptr(), n, Zc.data_ptr(), be.stream())
-        out = be.empty((p.size, cols), torch.float64)
-        _hip.columns_percentiles_dev(Zc.data_ptr(), cols, n, p, out.data_ptr(), be.stream())
-        be.synchronize()
-        return out.cpu().numpy().reshape(p.size, 2, ctx.N)

@@ -12,6 +12,8 @@ import warnings
 
 import numpy as np
 
+from .chainview import used_range
+
 _COLUMNS = ('freq', 'amp', 'pha', 'amp_err', 'pha_err')
 
 
@@ -153,6 +155,30 @@ def load_data_batch(spectra, headers=1, ph_units='mrad', threads=None):
     return tables_to_operands(T, ph_units)
 
 
+def first_if_scalar(p, out):
+    """``out``, one entry per percentile, as np.percentile gives it back: whole for a list ``p``, else its entry."""
+    return out if np.ndim(p) else out[0]
+
+
+def discard_thin(kwargs):
+    """The ``discard`` and ``thin`` keywords of a summary, with get_chain's defaults."""
+    return dict(discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1))
+
+
+def warn_if_nothing_discarded(kwargs):
+    """The reference's advice (src/bisip/utils.py:92-95) when the fitted chain is summarised whole."""
+    if 'discard' not in kwargs and 'thin' not in kwargs:
+        warnings.warn('No samples were discarded from the chain.\n'
+                      'Pass discard and thin keywords to remove burn-in samples and reduce autocorrelation.')
+
+
+def refuse_discard_of_a_chain(kwargs):
+    """An explicit chain is used as it is (src/bisip/utils.py:100-104)."""
+    if 'discard' in kwargs or 'thin' in kwargs:
+        raise ValueError('Please pass either a chain obtained with the get_chain() method or pass discard and '
+                         'thin keywords to parse the full chain. Do not pass both.')
+
+
 class utils(object):
     """Mixin with the reference's utility methods (src/bisip/utils.py:15)."""
 
@@ -164,17 +190,11 @@ class utils(object):
         if chain is None:
             kwargs['flat'] = True
             chain = self.get_chain(**kwargs)
-            if 'discard' not in kwargs and 'thin' not in kwargs:
-                warnings.warn('No samples were discarded from the chain.\n'
-                              'Pass discard and thin keywords to remove '
-                              'burn-in samples and reduce autocorrelation.', UserWarning)
+            warn_if_nothing_discarded(kwargs)
             return chain
         if chain.ndim > 2:
             raise ValueError('Flatten chain by passing flat=True.')
-        if 'discard' in kwargs or 'thin' in kwargs:
-            raise ValueError('Please pass either a chain obtained with the get_chain() '
-                             'method or pass discard and thin keywords to parse the full '
-                             'chain. Do not pass both.')
+        refuse_discard_of_a_chain(kwargs)
         return chain
 
     def get_model_percentile(self, p=[2.5, 50, 97.5], chain=None, **kwargs):
@@ -183,15 +203,13 @@ class utils(object):
         s = self._device_chain_sampler(chain, kwargs)
         if s is not None:       # fit(chain='device'): forward and percentiles where the chain lies
             try:
-                out = s.model_percentiles(p, discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1))
-                return out if np.ndim(p) else out[0]
+                return first_if_scalar(p, s.model_percentiles(p, **discard_thin(kwargs)))
             except NotImplementedError:
                 pass
         chain = np.ascontiguousarray(self.parse_chain(chain, **kwargs), dtype=np.float64)
         # forward over the chain and the percentiles over axis 0 both on the device: only the chain goes
         # up and (len(p), 2, N) comes back (bisip_forward_percentiles) -- np.percentile's own doubles
-        out = self._context().forward_percentiles(chain, p)
-        return out if np.ndim(p) else out[0]
+        return first_if_scalar(p, self._context().forward_percentiles(chain, p))
 
     def _device_chain_sampler(self, chain, kwargs, having='chain_on_device'):
         """The sampler, when its chain lives in HBM (fit(chain='device')) and the caller asked for a
@@ -204,32 +222,28 @@ class utils(object):
         extra = set(kwargs) - {'discard', 'thin', 'flat'}
         if extra:
             raise TypeError(f'unexpected keyword(s) {sorted(extra)}')
-        if 'discard' not in kwargs and 'thin' not in kwargs:      # same advice as parse_chain
-            warnings.warn('No samples were discarded from the chain.\n'
-                          'Pass discard and thin keywords to remove '
-                          'burn-in samples and reduce autocorrelation.', UserWarning)
+        warn_if_nothing_discarded(kwargs)      # same advice as parse_chain
         return s
 
     def get_param_percentile(self, p=[2.5, 50, 97.5], chain=None, **kwargs):
         """reference: src/bisip/utils.py:37-53"""
         s = self._device_chain_sampler(chain, kwargs)
         if s is not None:      # sorted and interpolated where the chain lies
-            out = s.param_percentiles(p, discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1))[:, 0, :]
-            return out if np.ndim(p) else out[0]
+            return first_if_scalar(p, s.param_percentiles(p, **discard_thin(kwargs))[:, 0, :])
         return np.percentile(self.parse_chain(chain, **kwargs), p, axis=0)
 
     def get_param_mean(self, chain=None, **kwargs):
         """reference: src/bisip/utils.py:55-69"""
         s = self._device_chain_sampler(chain, kwargs)
         if s is not None:
-            return s.param_moments(discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1))[0][0]
+            return s.param_moments(**discard_thin(kwargs))[0][0]
         return np.mean(self.parse_chain(chain, **kwargs), axis=0)
 
     def get_param_std(self, chain=None, **kwargs):
         """reference: src/bisip/utils.py:71-85"""
         s = self._device_chain_sampler(chain, kwargs)
         if s is not None:
-            return s.param_moments(discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1))[1][0]
+            return s.param_moments(**discard_thin(kwargs))[1][0]
         return np.std(self.parse_chain(chain, **kwargs), axis=0)
 
     def get_param_histogram(self, bins=25, range=None, chain=None, **kwargs):
@@ -243,8 +257,7 @@ class utils(object):
         bins = hg.check_bins(bins)
         s = self._device_chain_sampler(chain, kwargs, 'param_histograms')
         if s is not None:      # the device sampler: counted on the GPU, a host chain by upload of the used samples
-            counts, edges = s.param_histograms(bins, range, discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1),
-                                               bounds=self.param_bounds)
+            counts, edges = s.param_histograms(bins, range, bounds=self.param_bounds, **discard_thin(kwargs))
             return counts[0], edges[0]
         return hg.host_histograms(self.parse_chain(chain, **kwargs), bins, range, self.param_bounds)
 
@@ -257,8 +270,7 @@ class utils(object):
         bins = hg.check_bins(bins)
         s = self._device_chain_sampler(chain, kwargs, 'pair_histograms')
         if s is not None:
-            counts, edges, pairs = s.pair_histograms(bins, range, discard=kwargs.get('discard', 0),
-                                                     thin=kwargs.get('thin', 1), bounds=self.param_bounds)
+            counts, edges, pairs = s.pair_histograms(bins, range, bounds=self.param_bounds, **discard_thin(kwargs))
             return counts[0], edges[0], pairs
         return hg.host_pair_histograms(self.parse_chain(chain, **kwargs), bins, range, self.param_bounds)
 
@@ -271,10 +283,7 @@ class utils(object):
             chain = np.asarray(chain, dtype=np.float64)
             if chain.ndim != 3:
                 raise ValueError('A trace needs the unflattened chain (nsteps, nwalkers, ndim); do not pass flat=True.')
-            if 'discard' in kwargs or 'thin' in kwargs:
-                raise ValueError('Please pass either a chain obtained with the get_chain() '
-                                 'method or pass discard and thin keywords to parse the full '
-                                 'chain. Do not pass both.')
+            refuse_discard_of_a_chain(kwargs)
             return 'host', chain
         self._check_if_fitted()
         extra = set(kwargs) - {'discard', 'thin'}
@@ -283,8 +292,7 @@ class utils(object):
         s = self._sampler
         if getattr(s, 'trace_percentiles', None) is not None:
             return 'device', s
-        from .chainview import used_range
-        used_range(s.iteration, kwargs.get('discard', 0), kwargs.get('thin', 1))      # ValueError: no samples left
+        used_range(s.iteration, **discard_thin(kwargs))      # ValueError: no samples left
         return 'host', np.asarray(self.get_chain(**kwargs), dtype=np.float64)
 
     def get_trace_percentile(self, p=[2.5, 50, 97.5], chain=None, **kwargs):
@@ -297,17 +305,17 @@ class utils(object):
         pp = tr.check_percentiles(p)
         kind, src = self._trace_source(chain, kwargs)
         if kind == 'device':
-            out = src.trace_percentiles(pp, discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1))[:, :, 0, :]
+            out = src.trace_percentiles(pp, **discard_thin(kwargs))[:, :, 0, :]
         else:
             out = tr.host_trace(src, pp)[0]
-        return out if np.ndim(p) else out[0]
+        return first_if_scalar(p, out)
 
     def get_trace_mean(self, chain=None, **kwargs):
         """The mean over the walkers at every step, ``(n, ndim)``.  Arguments as get_trace_percentile."""
         from . import trace as tr
         kind, src = self._trace_source(chain, kwargs)
         if kind == 'device':
-            return src.trace_mean(discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1))[:, 0, :]
+            return src.trace_mean(**discard_thin(kwargs))[:, 0, :]
         return tr.host_trace(src, ())[1]
 
     def get_log_prob_trace(self, p=[2.5, 50, 97.5], **kwargs):
@@ -317,17 +325,17 @@ class utils(object):
         pp = tr.check_percentiles(p)
         kind, src = self._trace_source(None, kwargs)
         if kind == 'device':
-            out = src.log_prob_trace(pp, discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1))[:, :, 0]
+            out = src.log_prob_trace(pp, **discard_thin(kwargs))[:, :, 0]
         else:
-            lp = np.asarray(self._sampler.get_log_prob(discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1)))
+            lp = np.asarray(self._sampler.get_log_prob(**discard_thin(kwargs)))
             out = tr.host_trace(lp[:, :, None], pp)[0][:, :, 0]
-        return out if np.ndim(p) else out[0]
+        return first_if_scalar(p, out)
 
     def _walker_moments(self, chain, kwargs):
         from . import convergence as cv
         kind, src = self._trace_source(chain, kwargs)
         if kind == 'device':
-            mean, var = src.walker_moments(discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1))
+            mean, var = src.walker_moments(**discard_thin(kwargs))
             return mean[0], var[0]
         return cv.walker_moments(src)
 
@@ -342,7 +350,7 @@ class utils(object):
         from . import convergence as cv
         kind, src = self._trace_source(chain, kwargs)
         if kind == 'device':
-            return src.split_rhat(discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1), split=split)[0]
+            return src.split_rhat(split=split, **discard_thin(kwargs))[0]
         return cv.rhat(src, split=split)
 
     def get_walker_mean(self, chain=None, **kwargs):
@@ -360,8 +368,8 @@ class utils(object):
         from . import convergence as cv
         kind, src = self._trace_source(None, kwargs)
         if kind == 'device':
-            return float(src.log_prob_rhat(discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1), split=split)[0])
-        lp = np.asarray(self._sampler.get_log_prob(discard=kwargs.get('discard', 0), thin=kwargs.get('thin', 1)))
+            return float(src.log_prob_rhat(split=split, **discard_thin(kwargs))[0])
+        lp = np.asarray(self._sampler.get_log_prob(**discard_thin(kwargs)))
         return float(cv.rhat(lp[:, :, None], split=split)[0])
 
 

@@ -261,7 +261,7 @@ def test_spectra_batch_methods_on_a_host_chain():
     rng = np.random.default_rng(8)
     chain, lp = rng.normal(size=(30, 3, 6, 4)), rng.normal(size=(30, 3, 6))
     b = SpectraBatch.__new__(SpectraBatch)
-    b._histogram_sampler = lambda: _HostChainSampler(chain, lp)
+    b._fitted = lambda: _HostChainSampler(chain, lp)
     kw = dict(discard=4, thin=2)
     used = chain[5::2]
     assert b.get_rhat(**kw).shape == (3, 4)
