@@ -127,6 +127,15 @@ SYMBOLS = {
     'bisip_chain_rhat_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                             ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    'bisip_chain_cov_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    'bisip_chain_cov_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                           ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                           ctypes.c_void_p]),
+    'bisip_chain_best_sample_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    'bisip_chain_best_sample_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                                   ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_int64, ctypes.c_void_p]),
     'bisip_column_percentiles_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     'bisip_column_percentiles_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, _dp, ctypes.c_int,
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
@@ -822,6 +831,37 @@ def chain_rhat_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_p
                                                int(walkers_per_ensemble), int(ndim), int(splits), d_mean_ptr or None,
                                                d_var_ptr or None, d_rhat_ptr or None, d_work_ptr or None,
                                                int(work_bytes), stream))
+
+
+def chain_cov_workspace(n_samples, n_ensembles, walkers_per_ensemble, ndim):
+    """Bytes of device scratch chain_cov_dev needs (0: none; negative: shape not supported)."""
+    return int(load_library().bisip_chain_cov_workspace(int(n_samples), int(n_ensembles), int(walkers_per_ensemble), int(ndim)))
+
+
+def chain_cov_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, d_mean_ptr, d_cov_ptr,
+                  d_work_ptr=0, work_bytes=0, stream=0):
+    """``np.cov(rows.T, ddof=1)`` of every ensemble's used samples: d_cov (n_ensembles, ndim, ndim), d_mean (n_ensembles,
+    ndim) or 0 / None.  Device pointers (ints), asynchronous on ``stream``."""
+    _check(load_library().bisip_chain_cov_dev(d_chain_ptr or None, int(n_samples), int(sample_stride), int(n_ensembles),
+                                              int(walkers_per_ensemble), int(ndim), d_mean_ptr or None, d_cov_ptr or None,
+                                              d_work_ptr or None, int(work_bytes), stream))
+
+
+def chain_best_sample_workspace(n_samples, n_ensembles, walkers_per_ensemble):
+    """Bytes of device scratch chain_best_sample_dev needs (0: none; negative: shape not supported)."""
+    return int(load_library().bisip_chain_best_sample_workspace(int(n_samples), int(n_ensembles), int(walkers_per_ensemble)))
+
+
+def chain_best_sample_dev(d_chain_ptr, chain_stride, d_logp_ptr, logp_stride, n_samples, n_ensembles, walkers_per_ensemble,
+                          ndim, d_theta_ptr, d_best_logp_ptr, d_index_ptr, d_work_ptr=0, work_bytes=0, stream=0):
+    """The stored sample of largest log-probability of every ensemble: d_theta (n_ensembles, ndim), d_best_logp
+    (n_ensembles,), d_index (n_ensembles,) int64.  Each may be 0 / None, not all; the chain too when theta is.  Device
+    pointers (ints), asynchronous on ``stream``."""
+    _check(load_library().bisip_chain_best_sample_dev(d_chain_ptr or None, int(chain_stride), d_logp_ptr or None,
+                                                      int(logp_stride), int(n_samples), int(n_ensembles),
+                                                      int(walkers_per_ensemble), int(ndim), d_theta_ptr or None,
+                                                      d_best_logp_ptr or None, d_index_ptr or None, d_work_ptr or None,
+                                                      int(work_bytes), stream))
 
 
 def ensemble_gram_workspace(W, ndim):

@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _hip, decomposition
 from .autocorr import AutocorrError
+from .covariance import BatchCovariance
 from .dist import shard_range
 from .sampler import DeviceEnsembleSampler
 from .summaries import device_model_percentiles
@@ -46,7 +47,7 @@ def default_params(model, n_modes=1, poly_deg=5):
     return p
 
 
-class SpectraBatch:
+class SpectraBatch(BatchCovariance):
     """E spectra inverted together with the same model class.
 
     Args:

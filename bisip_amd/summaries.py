@@ -2,7 +2,8 @@
 
 ``DeviceChainSummaries`` is the part of ``DeviceEnsembleSampler`` that has nothing to do with sampling: it finds the
 used samples of the stored chain (or log-probability) on the device as a ChainView and hands that to the ``device_*``
-function of the family asked for (bisip_amd.chainview, .autocorr, .histogram, .trace, .convergence, .decomposition).
+function of the family asked for (bisip_amd.chainview, .autocorr, .histogram, .trace, .convergence, .covariance,
+.decomposition).
 ``device_model_percentiles`` also needs the model: forward over the samples, then the order statistics of each response.
 """
 
@@ -13,6 +14,7 @@ from . import histogram as hg
 from .autocorr import check_c, check_tol, device_integrated_time
 from .chainview import ChainView, _merge_device_parts, device_moments, device_percentiles, used_range
 from .convergence import device_rhat
+from .covariance import corr_from_cov, device_best_sample, device_cov
 from .trace import device_trace
 
 __all__ = ('DeviceChainSummaries', 'device_model_percentiles')
@@ -181,6 +183,24 @@ class DeviceChainSummaries:
     def log_prob_rhat(self, discard=0, thin=1, split=True):
         """R-hat of every ensemble's stored log-probability, ``(n_ensembles,)``, on the device."""
         return device_rhat(self.log_prob_samples_dev(discard, thin), split=split)[:, 0]
+
+    def param_cov(self, discard=0, thin=1):
+        """``np.cov`` (ddof = 1) of every ensemble's used samples flattened over its walkers -- of ``get_chain(discard,
+        thin, flat=True)`` restricted to the ensemble -- ``(n_ensembles, ndim, ndim)``, taken on the device
+        (bisip_chain_cov_dev) from the chain where it lies (``chain_on_device``), else from an upload of the used samples
+        only."""
+        return device_cov(self.used_samples_dev(discard, thin))
+
+    def param_corr(self, discard=0, thin=1):
+        """``np.corrcoef`` of the same samples, ``(n_ensembles, ndim, ndim)``: the device's covariance divided on the host
+        (covariance.corr_from_cov); NaN where a parameter does not vary."""
+        return corr_from_cov(self.param_cov(discard, thin))
+
+    def best_sample(self, discard=0, thin=1):
+        """The stored sample of largest log-probability among the used ones of every ensemble: ``(theta (n_ensembles,
+        ndim), logp (n_ensembles,), index (n_ensembles,))``, ``index = k * walkers_per_ensemble + w`` in used-sample
+        numbering, found on the device (bisip_chain_best_sample_dev)."""
+        return device_best_sample(self.used_samples_dev(discard, thin), self.log_prob_samples_dev(discard, thin))
 
     def _integrating_view(self, log_tau, norm_factor, discard, thin):
         view = self.used_samples_dev(discard, thin)

@@ -13,6 +13,7 @@ import warnings
 import numpy as np
 
 from .chainview import used_range
+from .covariance import ModelCovariance
 
 _COLUMNS = ('freq', 'amp', 'pha', 'amp_err', 'pha_err')
 
@@ -179,8 +180,9 @@ def refuse_discard_of_a_chain(kwargs):
                          'thin keywords to parse the full chain. Do not pass both.')
 
 
-class utils(object):
-    """Mixin with the reference's utility methods (src/bisip/utils.py:15)."""
+class utils(ModelCovariance):
+    """Mixin with the reference's utility methods (src/bisip/utils.py:15); the posterior covariance, correlation and best
+    sample come from bisip_amd.covariance.ModelCovariance."""
 
     def load_data(self, filename, headers=1, ph_units='mrad'):
         return load_data(filename, headers, ph_units)

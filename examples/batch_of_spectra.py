@@ -49,10 +49,20 @@ rhat = batch.gather(batch.get_rhat(discard=100))               # (E, ndim)
 wmean = batch.get_walker_mean(discard=100)                     # (E_rank, Wp, ndim)
 far = np.abs(wmean - mean[first:last, None, :]) > STUCK * std[first:last, None, :]
 stuck = batch.gather(far.any(axis=2).sum(axis=1))              # (E,) walkers per spectrum
+# how the parameters co-vary and the best stored sample, where the chain lies
+corr = batch.gather(batch.get_param_corr(discard=100))         # (E, ndim, ndim)
+theta_map, logp_map = batch.get_best_sample(discard=100)       # (E_rank, ndim), (E_rank,)
+logp_map = batch.gather(logp_map)
 if rank == 0:
     print('parameters', batch.param_names)
     for e in (0, 1, E - 1):
         print(f'spectrum {e:3d}  mean {np.round(mean[e], 3)}  median {np.round(p50[e], 3)}')
+    names = list(batch.param_names)
+    for e in (0, 1, E - 1):
+        off = np.where(np.eye(len(names), dtype=bool) | np.isnan(corr[e]), 0.0, np.abs(corr[e]))
+        j, k = np.unravel_index(np.argmax(off), off.shape)
+        print(f'spectrum {e:3d}  best log-probability {logp_map[e]:.3f}  most correlated pair {names[j]}, {names[k]}: '
+              f'{corr[e, j, k]:+.3f}')
     print('acceptance', round(float(accept.mean()), 3))
     print(f'{int((rhat.max(axis=1) > 1.05).sum())} of {E} spectra have max split R-hat > 1.05 (a screening number, beside '
           f'the autocorrelation time); {int(stuck.sum())} of {E * Wp} walkers lie more than {STUCK:g} posterior std from '

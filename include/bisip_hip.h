@@ -44,7 +44,8 @@ extern "C" {
  *    fp64_stream_probe_dev (+ _lanes), stretch_run_philox_dev (+ stretch_philox_inline) (additions only).
  * 5: chain_autocorr_time_dev (+ _workspace) (additions only).
  * 6: rtd_integrals_dev, rtd_columns_dev (additions only); chain_range_dev, chain_histograms_dev,
- *    chain_pair_histograms_dev, then chain_trace_dev (+ _workspace, _lds_walkers), then chain_rhat_dev (+ _workspace)
+ *    chain_pair_histograms_dev, then chain_trace_dev (+ _workspace, _lds_walkers), then chain_rhat_dev (+ _workspace),
+ *    then chain_cov_dev and chain_best_sample_dev (+ _workspace)
  *    came later under the same number (additions only: a caller that needs them looks the symbols up). */
 #define BISIP_ABI_VERSION 6
 
@@ -450,6 +451,44 @@ int64_t bisip_chain_rhat_workspace(int64_t n_samples, int64_t n_ensembles, int64
 int bisip_chain_rhat_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
                          int64_t walkers_per_ensemble, int ndim, int splits, double *d_mean, double *d_var,
                          double *d_rhat, void *d_work, int64_t work_bytes, void *stream);
+
+/* Posterior covariance of every ensemble's used samples of a chain resident in device memory: np.cov(rows.T, ddof=1) of
+ * the N = n_samples * walkers_per_ensemble rows that get_chain(discard, thin, flat=True) gives of the ensemble's walkers
+ * (bisip_amd/covariance.py holds the definitions: flat_cov, corr_from_cov).  Chain layout, d_chain / sample_stride
+ * conventions as for bisip_chain_moments_dev; ndim 1 ... BISIP_MAX_NDIM.  BISIP_EINVAL when N < 2.
+ *   d_cov (n_ensembles, ndim, ndim), full and symmetric: [j, k] and [k, j] hold the same bits.  d_mean (n_ensembles,
+ *   ndim), may be NULL.
+ * One pass with shifted sums: c_j = parameter j of walker 0 of the ensemble's first used sample, d = x - c, S_j = sum d_j,
+ * P_jk = sum d_j * d_k (the product rounded on its own, no fma), mean_j = c_j + S_j / N, cov_jk = (P_jk - (S_j * S_k) / N)
+ * / (N - 1); a diagonal entry < 0 becomes 0, a NaN stays.  A NaN or +-inf in parameter j of an ensemble makes row and
+ * column j of its matrix non-finite and nothing else.
+ * Order of every sum.  Rows are numbered r = k * walkers_per_ensemble + w.  n_ensembles >= 256: one segment of N rows;
+ * else want = 2048 / n_ensembles, seg_rows = max(1024, ceil(N / want)) (never above 2^30), nseg = ceil(N / seg_rows).
+ * Row i of a segment goes to slot i mod T, T = 256 for ndim <= 8 and 64 above; a slot adds its rows in ascending order
+ * from 0.0; the slots are added pairwise within each run of 64, 32, 16, ..., 1 apart, the four runs of T = 256 then in
+ * ascending order; segments in ascending order.  d_work: bisip_chain_cov_workspace() BYTES (0: none needed, one segment;
+ * < 0: shape not supported) for the segments' sums, 8-byte aligned.  The plan depends on the shape alone, never on the device.  No
+ * floating-point atomics: the same bits on every call (covariance.ordered_cov gives them in NumPy).  The chain is read
+ * once, whole 128-byte lines through LDS.  64-bit offsets.  Asynchronous on stream, no host synchronisation. */
+int64_t bisip_chain_cov_workspace(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim);
+int bisip_chain_cov_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+                        int64_t walkers_per_ensemble, int ndim, double *d_mean, double *d_cov,
+                        void *d_work, int64_t work_bytes, void *stream);
+
+/* The stored sample of largest log-probability of every ensemble -- the maximum-a-posteriori point of the run.  d_chain /
+ * chain_stride as above; d_logp (n_samples, n_ensembles * walkers_per_ensemble), sample k at d_logp + k * logp_stride.
+ *   d_index (n_ensembles): np.argmax(np.where(np.isnan(lp), -np.inf, lp)) over the ensemble's values in the order k *
+ *   walkers_per_ensemble + w: a NaN never wins, the lowest index wins among equals, 0 when all are NaN or -inf.
+ *   d_best_logp (n_ensembles): the stored value at that index, bit for bit.  d_theta (n_ensembles, ndim): that sample.
+ * Each of the three may be NULL, not all; d_chain may be NULL when d_theta is.  (value, index) pairs are compared, never
+ * values alone: exact whatever the order.  n_ensembles >= 256: one segment; else seg_rows = max(4096, ceil(N / (2048 /
+ * n_ensembles))).  d_work: bisip_chain_best_sample_workspace() BYTES (0: none needed; < 0: shape not supported), 8-byte aligned.
+ * Asynchronous on stream, no host synchronisation. */
+int64_t bisip_chain_best_sample_workspace(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble);
+int bisip_chain_best_sample_dev(const double *d_chain, int64_t chain_stride, const double *d_logp, int64_t logp_stride,
+                                int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim,
+                                double *d_theta, double *d_best_logp, int64_t *d_index,
+                                void *d_work, int64_t work_bytes, void *stream);
 
 /* np.percentile(rows, p, axis=0) for a device-resident (n_rows, n_cols) array (linear rule):
  * d_out (n_percentiles, n_cols).  Workspace in BYTES (0: more than 2^31 values). */
