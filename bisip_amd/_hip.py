@@ -151,6 +151,13 @@ SYMBOLS = {
                                                  ctypes.c_void_p, ctypes.c_void_p]),
     'bisip_forward_columns_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                                  ctypes.c_void_p, ctypes.c_void_p]),
+    'bisip_forward_columns_kind_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                                      ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    'bisip_forward_percentiles_kind': (ctypes.c_int, [ctypes.c_void_p, _dp, ctypes.c_int64, _dp, ctypes.c_int, ctypes.c_int, _dp]),
+    'bisip_response_moments_workspace': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    'bisip_response_moments_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                                  ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     'bisip_columns_percentiles_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int,
                                                      ctypes.c_void_p, ctypes.c_void_p]),
     'bisip_ctx_reduced_check': (ctypes.c_int, [ctypes.c_void_p, _dp, ctypes.c_int64, _dp, _dp]),
@@ -239,6 +246,19 @@ def _check(rc):
 
 def _c(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+RESPONSE_KINDS = {'ri': 0, 'pa': 1}      # BISIP_RESPONSE_RI, BISIP_RESPONSE_PA
+
+
+def response_kind(kind):
+    """BISIP_RESPONSE_* of 'ri' / 'pa'; an integer goes through as it is (the library refuses the ones it does not know)."""
+    if isinstance(kind, str):
+        try:
+            return RESPONSE_KINDS[kind]
+        except KeyError:
+            raise ValueError(f"kind must be 'ri' or 'pa', got {kind!r}") from None
+    return int(kind)
 
 
 def _p(a):
@@ -585,6 +605,19 @@ class HipContext:
         _check(rc)
         return out
 
+    def forward_percentiles_kind(self, theta, p, kind='ri'):
+        """``forward_percentiles`` in the representation ``kind``: 'ri' the same bits, 'pa' ``np.percentile`` of the
+        amplitude and of minus the phase of every sample's response (bisip_amd.response.response_pa)."""
+        theta = self._theta2d(theta)
+        p = _c(np.atleast_1d(p)).ravel()
+        out = np.empty((p.size, 2, self.N), dtype=np.float64)
+        rc = self._lib.bisip_forward_percentiles_kind(self._h, _p(theta), theta.shape[0], _p(p), p.size, response_kind(kind),
+                                                      _p(out))
+        if rc == -4:
+            raise NotImplementedError(self._lib.bisip_last_error().decode('utf-8', 'replace'))
+        _check(rc)
+        return out
+
     def loglike_z(self, Z):
         """Gaussian log-likelihood of caller-computed responses: Z (W, 2, N) host -> (W,) host."""
         Z = _c(Z)
@@ -613,6 +646,27 @@ class HipContext:
         column-major (n_spectra, 2N, W / n_spectra) -- what columns_percentiles_dev reads (device pointers)."""
         _check(self._lib.bisip_forward_columns_dev(self._h, int(first_spectrum), int(n_spectra), ctypes.c_void_p(d_theta_ptr),
                                                    int(W), ctypes.c_void_p(d_cols_ptr), ctypes.c_void_p(stream)))
+
+    def forward_columns_kind_dev(self, first_spectrum, n_spectra, d_theta_ptr, W, d_cols_ptr, kind='ri', stream=0):
+        """``forward_columns_dev`` in the representation ``kind``: 'pa' writes the amplitude into column j and minus the
+        phase into column N + j of every spectrum."""
+        _check(self._lib.bisip_forward_columns_kind_dev(self._h, int(first_spectrum), int(n_spectra), ctypes.c_void_p(d_theta_ptr),
+                                                        int(W), ctypes.c_void_p(d_cols_ptr), response_kind(kind),
+                                                        ctypes.c_void_p(stream)))
+
+    def response_moments_workspace(self, n_samples, n_spectra, walkers_per_ensemble):
+        """Bytes of device scratch response_moments_dev needs (0: none; negative: shape not supported)."""
+        return int(self._lib.bisip_response_moments_workspace(self._h, int(n_samples), int(n_spectra), int(walkers_per_ensemble)))
+
+    def response_moments_dev(self, first_spectrum, n_spectra, d_chain_ptr, n_samples, sample_stride, walkers_per_ensemble,
+                             kind, d_mean_ptr, d_std_ptr, d_work_ptr=0, work_bytes=0, stream=0):
+        """Mean and std (ddof = 0) of the model response over the used samples of ``n_spectra`` spectra: d_mean, d_std
+        (n_spectra, 2, N), either 0 / None.  ``d_chain_ptr``: walker 0 of ``first_spectrum`` in the first used sample.
+        Device pointers (ints), asynchronous on ``stream``."""
+        _check(self._lib.bisip_response_moments_dev(self._h, int(first_spectrum), int(n_spectra), d_chain_ptr or None,
+                                                    int(n_samples), int(sample_stride), int(walkers_per_ensemble),
+                                                    response_kind(kind), d_mean_ptr or None, d_std_ptr or None,
+                                                    d_work_ptr or None, int(work_bytes), ctypes.c_void_p(stream)))
 
     def forward_spectra_dev(self, first_spectrum, n_spectra, d_theta_ptr, W, d_Z_ptr, stream=0):
         """Batch context: forward of W rows over n_spectra consecutive spectra, W / n_spectra rows each

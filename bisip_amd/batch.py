@@ -13,6 +13,7 @@ from . import _hip, decomposition
 from .autocorr import AutocorrError
 from .covariance import BatchCovariance
 from .dist import shard_range
+from .response import BatchResponse
 from .sampler import DeviceEnsembleSampler
 from .summaries import device_model_percentiles
 from .utils import first_if_scalar, load_data_batch
@@ -47,7 +48,7 @@ def default_params(model, n_modes=1, poly_deg=5):
     return p
 
 
-class SpectraBatch(BatchCovariance):
+class SpectraBatch(BatchCovariance, BatchResponse):
     """E spectra inverted together with the same model class.
 
     Args:

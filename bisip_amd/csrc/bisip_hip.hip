@@ -945,14 +945,20 @@ int bisip_forward_spectra_dev(bisip_ctx *c, int64_t first_spectrum, int64_t n_sp
     return dispatch_forward(c, d_theta, W, d_Z, (hipStream_t)stream, first_spectrum, n_spectra);
 }
 
-int bisip_forward_columns_dev(bisip_ctx *c, int64_t first_spectrum, int64_t n_spectra, const double *d_theta, int64_t W,
-                              double *d_cols, void *stream)
+int bisip_forward_columns_kind_dev(bisip_ctx *c, int64_t first_spectrum, int64_t n_spectra, const double *d_theta, int64_t W,
+                                   double *d_cols, int kind, void *stream)
 {
     if (!c) return fail(BISIP_EINVAL, "null context");
     if (W < 0) return fail(BISIP_EINVAL, "W=%lld < 0", (long long)W);
     if (W > 0 && (!d_theta || !d_cols)) return fail(BISIP_EINVAL, "null buffer");
     HIP_TRY(hipSetDevice(c->device));
-    return dispatch_forward_columns(c, d_theta, W, d_cols, (hipStream_t)stream, first_spectrum, n_spectra);
+    return dispatch_forward_columns(c, d_theta, W, d_cols, (hipStream_t)stream, first_spectrum, n_spectra, kind);
+}
+
+int bisip_forward_columns_dev(bisip_ctx *c, int64_t first_spectrum, int64_t n_spectra, const double *d_theta, int64_t W,
+                              double *d_cols, void *stream)
+{
+    return bisip_forward_columns_kind_dev(c, first_spectrum, n_spectra, d_theta, W, d_cols, BISIP_RESPONSE_RI, stream);
 }
 
 int bisip_forward_spectrum_dev(bisip_ctx *c, int64_t spectrum, const double *d_theta, int64_t W, double *d_Z, void *stream)
@@ -1509,9 +1515,16 @@ int bisip_forward(bisip_ctx *c, const double *theta, int64_t W, double *Z)
 int bisip_forward_percentiles(bisip_ctx *c, const double *theta, int64_t W, const double *percentiles,
                               int n_percentiles, double *out)
 {
+    return bisip_forward_percentiles_kind(c, theta, W, percentiles, n_percentiles, BISIP_RESPONSE_RI, out);
+}
+
+int bisip_forward_percentiles_kind(bisip_ctx *c, const double *theta, int64_t W, const double *percentiles,
+                                   int n_percentiles, int kind, double *out)
+{
     if (!c) return fail(BISIP_EINVAL, "null context");
     if (c->E > 1) return fail(BISIP_EUNSUPPORTED, "bisip_forward_percentiles takes a single-spectrum context");
     if (W < 1 || !theta || !percentiles || !out || n_percentiles < 1) return fail(BISIP_EINVAL, "bad argument");
+    if (kind != BISIP_RESPONSE_RI && kind != BISIP_RESPONSE_PA) return fail(BISIP_EINVAL, "unknown response kind %d", kind);
     const int ncols = 2 * c->N;
     HIP_TRY(hipSetDevice(c->device));
     // the responses are written column by column (k_forward_columns) and the order statistics selected from
@@ -1524,7 +1537,7 @@ int bisip_forward_percentiles(bisip_ctx *c, const double *theta, int64_t W, cons
     char *base = (char *)c->d_ws;
     double *d_theta = (double *)base, *d_cols = (double *)(base + tb), *d_out = (double *)(base + tb + zb);
     HIP_TRY(hipMemcpyAsync(d_theta, theta, (size_t)W * c->ndim * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    rc = dispatch_forward_columns(c, d_theta, W, d_cols, c->stream, 0, 1);
+    rc = dispatch_forward_columns(c, d_theta, W, d_cols, c->stream, 0, 1, kind);
     if (rc != BISIP_OK) return rc;
     rc = bisip_columns_percentiles_dev(d_cols, ncols, W, percentiles, n_percentiles, d_out, c->stream);
     if (rc != BISIP_OK) return rc;

@@ -1,6 +1,6 @@
 // host.h -- what the translation units of libbisip_hip.so share: the context, the error
 // plumbing and the dispatch entry points.  The kernels are templates, so every dispatch_*.hip
-// instantiates only its own family and the four units compile in parallel.
+// instantiates only its own family and the units compile in parallel.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -157,7 +157,7 @@ int dispatch_logprob(const bisip_ctx *c, const double *theta, int64_t W, double 
 int dispatch_forward(const bisip_ctx *c, const double *theta, int64_t W, double *Z, hipStream_t st, long long spectrum = -1,
                      long long count = 1);
 int dispatch_forward_columns(const bisip_ctx *c, const double *theta, int64_t W, double *cols, hipStream_t st, long long spectrum,
-                             long long count);
+                             long long count, int kind = BISIP_RESPONSE_RI);
 
 // dispatch_stretch.hip
 enum StretchKind { STRETCH_HALF, STRETCH_EVAL, STRETCH_PERSIST, STRETCH_GROUP };

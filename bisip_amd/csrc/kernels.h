@@ -2074,7 +2074,23 @@ __global__ __launch_bounds__(64) void k_forward_tiled16(const LaunchArgs a)
 // What the percentile kernels read (chain_stats.hip), so the model-space bands of a survey need no
 // row -> column transposition (a 27 GB round trip for 4096 spectra): lane = walker, every store instruction
 // writes 64 consecutive doubles of one column, no LDS staging needed.  Same M::eval, same values as Z.
-template <class M>
+// PA (BISIP_RESPONSE_PA): column j holds the amplitude hypot(re, im) and column N + j MINUS the phase, -atan2(im, re), in
+// rad (bisip_amd/response.py: response_pa) -- the device library's hypot and atan2 of every sample's own response, so
+// that the selection kernel reads amplitude / phase columns exactly as it reads Re / Im ones.  (The amplitude is NOT
+// selected on re * re + im * im with the root taken afterwards: one code path for both columns.)
+template <bool PA>
+__device__ __forceinline__ void store_response(double zr, double zi, double *__restrict__ c0, double *__restrict__ c1)
+{
+    if constexpr (PA) {
+        __builtin_nontemporal_store(hypot(zr, zi), c0);
+        __builtin_nontemporal_store(-atan2(zi, zr), c1);
+    } else {
+        __builtin_nontemporal_store(zr, c0);
+        __builtin_nontemporal_store(zi, c1);
+    }
+}
+
+template <class M, bool PA = false>
 __global__ __launch_bounds__(64) void k_forward_columns(const LaunchArgs a)
 {
     constexpr int NDIM = M::NDIM;
@@ -2095,8 +2111,7 @@ __global__ __launch_bounds__(64) void k_forward_columns(const LaunchArgs a)
         for (int j = 0; j < N; ++j) {
             double zr, zi;
             eval_const<M>(s, cb + (long long)j * M::REC, zr, zi);
-            __builtin_nontemporal_store(zr, col + (long long)j * Wp);
-            __builtin_nontemporal_store(zi, col + (long long)(N + j) * Wp);
+            store_response<PA>(zr, zi, col + (long long)j * Wp, col + (long long)(N + j) * Wp);
         }
         return;
     }
@@ -2104,8 +2119,7 @@ __global__ __launch_bounds__(64) void k_forward_columns(const LaunchArgs a)
     for (int j = 0; j < N; ++j) {
         double zr, zi;
         M::eval(s, cb + (long long)j * M::REC + 4, zr, zi);
-        __builtin_nontemporal_store(zr, col + (long long)j * Wp);
-        __builtin_nontemporal_store(zi, col + (long long)(N + j) * Wp);
+        store_response<PA>(zr, zi, col + (long long)j * Wp, col + (long long)(N + j) * Wp);
     }
 }
 

@@ -3,7 +3,7 @@
 ``DeviceChainSummaries`` is the part of ``DeviceEnsembleSampler`` that has nothing to do with sampling: it finds the
 used samples of the stored chain (or log-probability) on the device as a ChainView and hands that to the ``device_*``
 function of the family asked for (bisip_amd.chainview, .autocorr, .histogram, .trace, .convergence, .covariance,
-.decomposition).
+.decomposition, .response).
 ``device_model_percentiles`` also needs the model: forward over the samples, then the order statistics of each response.
 """
 
@@ -15,16 +15,18 @@ from .autocorr import check_c, check_tol, device_integrated_time
 from .chainview import ChainView, _merge_device_parts, device_moments, device_percentiles, used_range
 from .convergence import device_rhat
 from .covariance import corr_from_cov, device_best_sample, device_cov
+from .response import device_model_moments
 from .trace import device_trace
 
 __all__ = ('DeviceChainSummaries', 'device_model_percentiles')
 
 
-def device_model_percentiles(view, ctx, p):
+def device_model_percentiles(view, ctx, p, kind='ri'):
     """``np.percentile`` of the model response of ``ctx`` (a HipContext of ``view.n_ensembles`` spectra) over every
     ensemble's samples of a ChainView: ``(len(p), n_ensembles, 2 * N)`` (NumPy).  Spectra go in passes whose responses
     stay under ``decomposition.RTD_PASS_BYTES``: one forward launch that writes them column by column, one selection of
-    the order statistics from each column."""
+    the order statistics from each column.  ``kind='pa'``: the columns hold every sample's amplitude and minus phase
+    (bisip_amd.response.response_pa) instead of Re and Im; everything else is the same."""
     import torch
     n, E, Wp, ndim = view.n, view.n_ensembles, view.walkers_per_ensemble, view.ndim
     p = np.atleast_1d(np.asarray(p, dtype=np.float64))
@@ -36,7 +38,10 @@ def device_model_percentiles(view, ctx, p):
         k = min(E, g0 + G) - g0
         rows = grid[:, g0:g0 + k].permute(1, 0, 2, 3).reshape(k, rows_per, ndim)    # one copy: spectrum-major
         Zc = view.empty((k, cols, rows_per), torch.float64)                       # one column per (spectrum, part, frequency)
-        ctx.forward_columns_dev(g0, k, rows.data_ptr(), k * rows_per, Zc.data_ptr(), view.stream)
+        if kind == 'ri':
+            ctx.forward_columns_dev(g0, k, rows.data_ptr(), k * rows_per, Zc.data_ptr(), view.stream)
+        else:
+            ctx.forward_columns_kind_dev(g0, k, rows.data_ptr(), k * rows_per, Zc.data_ptr(), kind, view.stream)
         res = view.empty((p.size, k * cols), torch.float64)
         _hip.columns_percentiles_dev(Zc.data_ptr(), k * cols, rows_per, p, res.data_ptr(), view.stream)
         view.synchronize()
@@ -235,3 +240,22 @@ class DeviceChainSummaries:
             raise NotImplementedError('model percentiles of a batch of spectra: one spectrum at a time')
         ctx = self.backend.ctx
         return device_model_percentiles(self.used_samples_dev(discard, thin, upload=False), ctx, p).reshape(-1, 2, ctx.N)
+
+    def model_percentiles_pa(self, p=(2.5, 50, 97.5), discard=0, thin=1):
+        """``np.percentile(response_pa(forward(get_chain(discard, thin, flat=True))), p, axis=0)``: the percentiles of
+        every sample's amplitude and minus phase (bisip_amd.response), as model_percentiles -- the forward kernel writes
+        amplitude / phase columns, the same selection reads them.  One ensemble only (NotImplementedError otherwise);
+        returns ``(len(p), 2, N)``."""
+        if self.n_ensembles != 1:
+            raise NotImplementedError('model percentiles of a batch of spectra: one spectrum at a time')
+        ctx = self.backend.ctx
+        out = device_model_percentiles(self.used_samples_dev(discard, thin, upload=False), ctx, p, 'pa')
+        return out.reshape(-1, 2, ctx.N)
+
+    def model_moments(self, kind='ri', discard=0, thin=1):
+        """``(mean, std)`` of the model response over every ensemble's used samples, ``(n_ensembles, 2, N)`` each, in the
+        representation ``kind`` ('ri': Re and Im; 'pa': amplitude and minus phase): ``np.mean`` / ``np.std`` (ddof = 0)
+        of ``forward(get_chain(discard, thin, flat=True))`` per ensemble, evaluated and summed in one pass over the chain
+        where it lies (bisip_response_moments_dev; ``chain_on_device``), else over an upload of the used samples only.
+        No response is stored."""
+        return device_model_moments(self.used_samples_dev(discard, thin), self.backend.ctx, kind)

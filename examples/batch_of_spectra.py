@@ -52,6 +52,7 @@ stuck = batch.gather(far.any(axis=2).sum(axis=1))              # (E,) walkers pe
 # how the parameters co-vary and the best stored sample, where the chain lies
 corr = batch.gather(batch.get_param_corr(discard=100))         # (E, ndim, ndim)
 theta_map, logp_map = batch.get_best_sample(discard=100)       # (E_rank, ndim), (E_rank,)
+amp_pha, zmean = batch.get_model_percentile_pa([2.5, 50, 97.5], discard=100), batch.get_model_mean('pa', discard=100)   # (3, E_rank, 2, N), (E_rank, 2, N): amplitude and minus phase
 logp_map = batch.gather(logp_map)
 if rank == 0:
     print('parameters', batch.param_names)

@@ -45,7 +45,8 @@ extern "C" {
  * 5: chain_autocorr_time_dev (+ _workspace) (additions only).
  * 6: rtd_integrals_dev, rtd_columns_dev (additions only); chain_range_dev, chain_histograms_dev,
  *    chain_pair_histograms_dev, then chain_trace_dev (+ _workspace, _lds_walkers), then chain_rhat_dev (+ _workspace),
- *    then chain_cov_dev and chain_best_sample_dev (+ _workspace)
+ *    then chain_cov_dev and chain_best_sample_dev (+ _workspace), then forward_columns_kind_dev,
+ *    forward_percentiles_kind and response_moments_dev (+ _workspace) with BISIP_RESPONSE_RI / _PA
  *    came later under the same number (additions only: a caller that needs them looks the symbols up). */
 #define BISIP_ABI_VERSION 6
 
@@ -73,6 +74,10 @@ extern "C" {
 #define BISIP_ENOMEM     -3
 #define BISIP_EUNSUPPORTED -4
 #define BISIP_ERCCL     -5 /* an RCCL call failed                                   */
+
+/* representation of a model response (bisip_amd/response.py) */
+#define BISIP_RESPONSE_RI 0 /* real and imaginary part: what forward returns                          */
+#define BISIP_RESPONSE_PA 1 /* amplitude hypot(re, im) and MINUS the phase, -atan2(im, re), in rad    */
 
 #define BISIP_MAX_NDIM 16
 #define BISIP_MAX_MODES 5
@@ -138,6 +143,14 @@ int bisip_forward_spectrum_dev(bisip_ctx *ctx, int64_t spectrum, const double *d
  * a survey need no transposition.  Any number of rows per spectrum. */
 int bisip_forward_columns_dev(bisip_ctx *ctx, int64_t first_spectrum, int64_t n_spectra, const double *d_theta,
                               int64_t W, double *d_cols, void *stream);
+/* ... in the representation `kind` (BISIP_RESPONSE_*).  RI: the same kernel and the same bits as
+ * bisip_forward_columns_dev.  PA: column j of a spectrum holds the amplitude hypot(re, im) and column N + j MINUS the
+ * phase, -atan2(im, re), in rad and in [-pi, pi] (no unwrapping) -- the device library's hypot and atan2 of every
+ * sample's own response (the amplitude is not selected on re * re + im * im), so bisip_columns_percentiles_dev gives
+ * the amplitude / phase bands of the posterior from these columns as it gives the Re / Im ones: no second kernel, no
+ * second pass.  BISIP_EINVAL for any other kind. */
+int bisip_forward_columns_kind_dev(bisip_ctx *ctx, int64_t first_spectrum, int64_t n_spectra, const double *d_theta,
+                                   int64_t W, double *d_cols, int kind, void *stream);
 /* ... or to n_spectra consecutive spectra starting with first_spectrum, W / n_spectra rows each
  * (a multiple of 64 when n_spectra > 1), in one launch. */
 int bisip_forward_spectra_dev(bisip_ctx *ctx, int64_t first_spectrum, int64_t n_spectra, const double *d_theta,
@@ -518,6 +531,39 @@ int bisip_grouped_percentiles_dev(const double *d_rows, int64_t n_groups, int64_
  * statistics selected from the columns: the same doubles as np.percentile).  Single-spectrum contexts. */
 int bisip_forward_percentiles(bisip_ctx *ctx, const double *theta, int64_t W,
                               const double *percentiles, int n_percentiles, double *out);
+/* The same in the representation `kind` (BISIP_RESPONSE_*): PA gives np.percentile of the amplitude and of minus the
+ * phase of every sample's response, out (n_percentiles, 2, N); RI the bits of bisip_forward_percentiles. */
+int bisip_forward_percentiles_kind(bisip_ctx *ctx, const double *theta, int64_t W, const double *percentiles,
+                                   int n_percentiles, int kind, double *out);
+
+/* Mean and standard deviation (ddof = 0) of the MODEL RESPONSE over the used samples of a chain resident in device memory,
+ * for n_spectra consecutive spectra of the context starting with first_spectrum: np.mean / np.std over axis 0 of forward
+ * (kind RI) or of its amplitude and minus phase (kind PA) of the R = n_samples * walkers_per_ensemble rows that
+ * get_chain(discard, thin, flat=True) gives of each spectrum's walkers (bisip_amd/response.py holds the definitions:
+ * response_pa, response_moments).  Fused: the chain is read where it lies, the model evaluated in registers; no response
+ * is written to memory.
+ *   d_chain: walker 0 of spectrum first_spectrum in the first used sample; sample k at d_chain + k * sample_stride
+ *   (doubles), row (e * walkers_per_ensemble + w) * ndim of it belongs to walker w of spectrum first_spectrum + e --
+ *   discard / thin are a pointer offset and a stride multiple, as for bisip_chain_moments_dev.
+ *   d_mean, d_std (n_spectra, 2, N) each; either may be NULL, not both.
+ * One pass with shifted sums per (part, frequency): c = the response of walker 0 of the spectrum's first used sample,
+ * d = x - c, S = sum d, P = sum d * d (the product rounded on its own, no fma), mean = c + S / R, var = (P - (S * S) / R)
+ * / R with < 0 -> 0 (a NaN stays), std = sqrt(var).  A row with a parameter that is not finite counts as NaN: it makes
+ * the means and stds of ITS spectrum non-finite and no other spectrum's.
+ * Order of every sum.  Rows are numbered r = k * walkers_per_ensemble + w.  n_spectra >= 256: one segment of R rows;
+ * else want = 2048 / n_spectra, seg_rows = max(1024, ceil(R / want)) (never above 2^30), nseg = ceil(R / seg_rows).  A
+ * workgroup of 256 threads takes one (spectrum, segment): row i of the segment goes to slot i mod 256; a slot adds its
+ * rows in ascending order from 0.0; the slots are added pairwise within each run of 64, 32, 16, ..., 1 apart, the four
+ * runs then in ascending order; segments in ascending order.  (The frequencies go in tiles of 8, each a pass over the
+ * segment's rows: 32 running sums per lane; the tiling changes no sum.)  d_work:
+ * bisip_response_moments_workspace() BYTES (0: none needed, one segment; < 0: shape not supported) for the segments'
+ * sums and the shifts, 8-byte aligned.  The plan depends on the shape alone, never on the device.  No floating-point
+ * atomics: the same bits on every call (response.ordered_response_moments gives them in NumPy from the same responses).
+ * 64-bit offsets.  Asynchronous on stream, no host synchronisation.  BISIP_EINVAL for an unknown kind. */
+int64_t bisip_response_moments_workspace(bisip_ctx *ctx, int64_t n_samples, int64_t n_spectra, int64_t walkers_per_ensemble);
+int bisip_response_moments_dev(bisip_ctx *ctx, int64_t first_spectrum, int64_t n_spectra, const double *d_chain,
+                               int64_t n_samples, int64_t sample_stride, int64_t walkers_per_ensemble, int kind,
+                               double *d_mean, double *d_std, void *d_work, int64_t work_bytes, void *stream);
 
 /* Host: the stretch move's random stream in numpy.random.RandomState order for n_steps
  * iterations of a W-walker ensemble (the contract is bisip_amd/sampler.py:draw_step).
