@@ -136,6 +136,11 @@ SYMBOLS = {
                                                    ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_int64, ctypes.c_void_p]),
+    'bisip_chain_hdi_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.POINTER(ctypes.c_int64)]),
+    'bisip_chain_hdi_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                           ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     'bisip_column_percentiles_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     'bisip_column_percentiles_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, _dp, ctypes.c_int,
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
@@ -916,6 +921,29 @@ def chain_best_sample_dev(d_chain_ptr, chain_stride, d_logp_ptr, logp_stride, n_
                                                       int(walkers_per_ensemble), int(ndim), d_theta_ptr or None,
                                                       d_best_logp_ptr or None, d_index_ptr or None, d_work_ptr or None,
                                                       int(work_bytes), stream))
+
+
+def _windows_array(windows):
+    w = [int(k) for k in np.atleast_1d(windows)]
+    return (ctypes.c_int64 * max(1, len(w)))(*w), len(w)
+
+
+def chain_hdi_workspace(n_samples, n_ensembles, walkers_per_ensemble, ndim, windows):
+    """Bytes of device scratch chain_hdi_dev needs for the windows ``K`` (negative: shape or windows refused)."""
+    w, nw = _windows_array(windows)
+    return int(load_library().bisip_chain_hdi_workspace(int(n_samples), int(n_ensembles), int(walkers_per_ensemble), int(ndim),
+                                                        nw, w))
+
+
+def chain_hdi_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, windows, d_out_ptr,
+                  d_index_ptr=0, d_work_ptr=0, work_bytes=0, stream=0):
+    """Highest-density intervals of every ensemble's used samples for the windows ``K = floor(mass * N)``: d_out
+    (len(windows), 2, n_ensembles, ndim), d_index (len(windows), n_ensembles, ndim) int64 or 0 / None.  Device pointers
+    (ints), asynchronous on ``stream``."""
+    w, nw = _windows_array(windows)
+    _check(load_library().bisip_chain_hdi_dev(d_chain_ptr or None, int(n_samples), int(sample_stride), int(n_ensembles),
+                                              int(walkers_per_ensemble), int(ndim), w, nw, d_out_ptr or None,
+                                              d_index_ptr or None, d_work_ptr or None, int(work_bytes), stream))
 
 
 def ensemble_gram_workspace(W, ndim):

@@ -125,6 +125,7 @@ struct SelectArgs {
     double t[SEL_MAX_P];       // weight of the upper one
     double *out;               // (n_p, columns): percentile k of column c at out[k * out_stride + c]
     long long out_stride;
+    int raw;                   // 1: write order statistic lo[k] itself, bit for bit, instead of the interpolation
 };
 
 // One 1024-lane workgroup per column, narrowing a RANGE of keys and finishing by counting.  VPT > 0: the
@@ -313,8 +314,9 @@ void k_segmented_select(const SelectArgs a)
     if (tid < a.n_p) {
         const double x = select_value(base[2 * tid]), y = select_value(base[2 * tid + 1]), t = a.t[tid];
         const double d = y - x;
-        // numpy.lib._function_base_impl._lerp, as k_percentile_lerp
-        a.out[(long long)tid * a.out_stride + col] = t >= 0.5 ? y - d * (1.0 - t) : x + d * t;
+        // numpy.lib._function_base_impl._lerp, as k_percentile_lerp (raw: x + (y - x) * 0 would turn -0.0 into +0.0 and
+        // an infinite step into NaN)
+        a.out[(long long)tid * a.out_stride + col] = a.raw ? x : (t >= 0.5 ? y - d * (1.0 - t) : x + d * t);
     }
 }
 
@@ -377,15 +379,16 @@ int percentile_ranks(long long n, const double *percentiles, int n_percentiles, 
 }
 
 // the order statistics of `columns` contiguous columns of n values, SEL_MAX_P percentiles per launch; percentile k
-// of column c goes to d_out[k * out_stride + c] (out_stride 0: columns)
+// of column c goes to d_out[k * out_stride + c] (out_stride 0: columns); raw: order statistic lo[k] itself
 int select_columns(const double *cols, long long n, long long columns, int n_percentiles, const std::vector<long long> &lo,
-                   const std::vector<double> &t, double *d_out, hipStream_t st, long long out_stride)
+                   const std::vector<double> &t, double *d_out, hipStream_t st, long long out_stride, bool raw)
 {
     if (out_stride <= 0) out_stride = columns;
     for (int k0 = 0; k0 < n_percentiles; k0 += SEL_MAX_P) {
         SelectArgs sa{};
         sa.cols = cols; sa.n = n; sa.columns = columns; sa.out = d_out + (long long)k0 * out_stride; sa.out_stride = out_stride;
         sa.n_p = n_percentiles - k0 < SEL_MAX_P ? n_percentiles - k0 : SEL_MAX_P;
+        sa.raw = raw ? 1 : 0;
         for (int k = 0; k < sa.n_p; ++k) { sa.lo[k] = lo[k0 + k]; sa.t[k] = t[k0 + k]; }
         if (n <= 1024 * 8) hipLaunchKernelGGL(k_segmented_select<8>, dim3((unsigned)columns), dim3(1024), 0, st, sa);
         else if (n <= 1024 * 16) hipLaunchKernelGGL(k_segmented_select<16>, dim3((unsigned)columns), dim3(1024), 0, st, sa);
@@ -393,6 +396,22 @@ int select_columns(const double *cols, long long n, long long columns, int n_per
         else hipLaunchKernelGGL(k_segmented_select<0>, dim3((unsigned)columns), dim3(1024), 0, st, sa);
         HIP_TRY(hipGetLastError());
     }
+    return BISIP_OK;
+}
+
+// samples (n_samples, E*Wp, ndim) -> cols (E*ndim, n_samples*Wp): one contiguous column per (ensemble, parameter), value
+// k * Wp + w from sample k, walker w (k_gather_columns; the tiled kernel from ndim = 16 on)
+int gather_columns(const double *d_chain, long long n_samples, long long sample_stride, long long E, long long Wp, int ndim,
+                   double *cols, hipStream_t st)
+{
+    GatherArgs g{d_chain, n_samples, sample_stride, E, Wp, ndim, cols};
+    const long long rows = n_samples * E * Wp;
+    const long long tiles = n_samples * E * ((Wp + 63) / 64) * ((ndim + 63) / 64);
+    if (ndim >= 16 && tiles <= 0x7fffffffLL)
+        hipLaunchKernelGGL(k_gather_columns_tiled, dim3((unsigned)tiles), dim3(256), 0, st, g);
+    else
+        hipLaunchKernelGGL(k_gather_columns, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, g);
+    HIP_TRY(hipGetLastError());
     return BISIP_OK;
 }
 
@@ -516,14 +535,8 @@ int percentiles_impl(const double *d_chain, int64_t n_samples, int64_t sample_st
     rc = percentile_ranks(n, percentiles, n_percentiles, lo, t);
     if (rc != BISIP_OK) return rc;
 
-    GatherArgs g{d_chain, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, cols};
-    const long long rows = n_samples * n_ensembles * walkers_per_ensemble;
-    const long long tiles = n_samples * n_ensembles * ((walkers_per_ensemble + 63) / 64) * ((ndim + 63) / 64);
-    if (ndim >= 16 && tiles <= 0x7fffffffLL)
-        hipLaunchKernelGGL(k_gather_columns_tiled, dim3((unsigned)tiles), dim3(256), 0, st, g);
-    else
-        hipLaunchKernelGGL(k_gather_columns, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, g);
-    HIP_TRY(hipGetLastError());
+    rc = gather_columns(d_chain, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, cols, st);
+    if (rc != BISIP_OK) return rc;
     // Select, do not sort: up to SEL_MAX_P percentiles per launch, one workgroup per column.  More percentiles
     // than that go through in groups when the columns are few (a handful of very long columns is where the
     // segmented sort is at its worst: benchmarks/micro/select_long_columns.py); with many columns AND many

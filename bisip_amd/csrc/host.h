@@ -175,10 +175,12 @@ int dispatch_stretch(const bisip_ctx *c, const StretchWork &a, long long Wp, hip
 int dispatch_stretch_batch(const bisip_ctx *c, const StretchWork &a, long long Wp, hipStream_t st);   // dispatch_stretch_batch.hip
 int dispatch_apply(const bisip_ctx *c, const StretchArgs &a, hipStream_t st);
 
-// chain_stats.hip: what the percentile entry points share with chain_trace.hip
+// chain_stats.hip: what the percentile entry points share with chain_trace.hip and chain_hdi.hip
 int percentile_ranks(long long n, const double *percentiles, int n_percentiles, std::vector<long long> &lo, std::vector<double> &t);
 int select_columns(const double *cols, long long n, long long columns, int n_percentiles, const std::vector<long long> &lo,
-                   const std::vector<double> &t, double *d_out, hipStream_t st, long long out_stride = 0);
+                   const std::vector<double> &t, double *d_out, hipStream_t st, long long out_stride = 0, bool raw = false);
+int gather_columns(const double *d_chain, long long n_samples, long long sample_stride, long long E, long long Wp, int ndim,
+                   double *cols, hipStream_t st);
 int gather_columns_by_sample(const double *d_chain, long long n_samples, long long sample_stride, long long E, long long Wp,
                              int ndim, double *cols, hipStream_t st);
 

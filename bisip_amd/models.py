@@ -20,6 +20,7 @@ from . import _hip
 from . import decomposition as _decomp
 from . import utils as _utils
 from .chainview import ChainView, device_moments, device_percentiles, used_range
+from .interval import DecompositionIntervals
 from .plotlib import plotlib as _plotlib
 from .sampler import DeviceEnsembleSampler, EnsembleSampler
 
@@ -339,7 +340,7 @@ class Inversion(_plotlib, _utils.utils):
         return np.array(list(self.params.values()), dtype=np.float64).T
 
 
-class PolynomialDecomposition(Inversion):
+class PolynomialDecomposition(DecompositionIntervals, Inversion):
     """Debye / Warburg polynomial decomposition (reference: src/bisip/models.py:182-229).
 
     Args:

@@ -3,7 +3,7 @@
 ``DeviceChainSummaries`` is the part of ``DeviceEnsembleSampler`` that has nothing to do with sampling: it finds the
 used samples of the stored chain (or log-probability) on the device as a ChainView and hands that to the ``device_*``
 function of the family asked for (bisip_amd.chainview, .autocorr, .histogram, .trace, .convergence, .covariance,
-.decomposition, .response).
+.interval, .decomposition, .response).
 ``device_model_percentiles`` also needs the model: forward over the samples, then the order statistics of each response.
 """
 
@@ -15,6 +15,7 @@ from .autocorr import check_c, check_tol, device_integrated_time
 from .chainview import ChainView, _merge_device_parts, device_moments, device_percentiles, used_range
 from .convergence import device_rhat
 from .covariance import corr_from_cov, device_best_sample, device_cov
+from .interval import device_hdi
 from .response import device_model_moments
 from .trace import device_trace
 
@@ -207,6 +208,13 @@ class DeviceChainSummaries:
         numbering, found on the device (bisip_chain_best_sample_dev)."""
         return device_best_sample(self.used_samples_dev(discard, thin), self.log_prob_samples_dev(discard, thin))
 
+    def param_hdi(self, mass=0.95, discard=0, thin=1):
+        """The highest-density interval of every parameter of every ensemble over ``get_chain(discard, thin,
+        flat=True)`` restricted to the ensemble (bisip_amd.interval.hdi): ``(2, n_ensembles, ndim)``, or ``(len(mass), 2,
+        n_ensembles, ndim)`` for a sequence of masses, taken on the device (bisip_chain_hdi_dev) from the chain where it
+        lies (``chain_on_device``), else from an upload of the used samples only."""
+        return device_hdi(self.used_samples_dev(discard, thin), mass)
+
     def _integrating_view(self, log_tau, norm_factor, discard, thin):
         view = self.used_samples_dev(discard, thin)
         return view.derived(decomposition.device_integrating_chain(view, log_tau, norm_factor))
@@ -224,6 +232,11 @@ class DeviceChainSummaries:
     def integrating_percentiles(self, p, log_tau, norm_factor, discard=0, thin=1):
         """np.percentile of the integrating parameters per ensemble, ``(len(p), n_ensembles, 3)``, on the device."""
         return device_percentiles(self._integrating_view(log_tau, norm_factor, discard, thin), p)
+
+    def integrating_hdi(self, mass, log_tau, norm_factor, discard=0, thin=1):
+        """The highest-density interval of the integrating parameters per ensemble, ``(2, n_ensembles, 3)`` (``(len(mass),
+        2, n_ensembles, 3)`` for a sequence of masses), on the device."""
+        return device_hdi(self._integrating_view(log_tau, norm_factor, discard, thin), mass)
 
     def rtd_percentiles(self, p, log_tau, discard=0, thin=1):
         """np.percentile of the RTD ``m_l`` per ensemble, ``(len(p), n_ensembles, L)``, on the device

@@ -503,6 +503,41 @@ int bisip_chain_best_sample_dev(const double *d_chain, int64_t chain_stride, con
                                 double *d_theta, double *d_best_logp, int64_t *d_index,
                                 void *d_work, int64_t work_bytes, void *stream);
 
+/* Highest-density intervals of every parameter, per ensemble, of a chain resident in device memory: the shortest interval
+ * that holds a given share of each column's values (ArviZ's unimodal hdi; bisip_amd/interval.py holds the definition in
+ * NumPy).  Chain layout, d_chain / sample_stride conventions as for bisip_chain_moments_dev (discard: an offset, thin: a
+ * stride, padding allowed); ndim 1 ... BISIP_MAX_NDIM.  A column is one parameter of one ensemble over its N = n_samples *
+ * walkers_per_ensemble values, numbered k * walkers_per_ensemble + w; s is the column sorted.  windows: host array
+ * (n_windows,), 1 <= n_windows <= 8, of K = floor(mass * N) computed by the caller, each in [1, N - 1] (so N >= 2); M = N - K.
+ *   width[i] = s[i + K] - s[i], i = 0 ... M - 1; a NaN width (inf - inf) is read as +inf; i* = the lowest i of smallest
+ *   width; the interval is (s[i*], s[i* + K]).  A column that holds a NaN gives (NaN, NaN) and i* = 0.
+ *   d_out (n_windows, 2, n_ensembles, ndim): lower ends, then upper ends.  d_index (n_windows, n_ensembles, ndim): i*, may
+ *   be NULL.
+ * Subtractions and comparisons of the same doubles as the definition: equal results (the sign of a zero is not pinned).
+ * Two paths, the same results.  full: the columns are gathered, all sorted (segmented radix sort), and one workgroup per
+ * (column, window) takes the argmin over (width, i).  tails: only s[0 .. M-1] and s[K .. N-1] are ever read, so the order
+ * statistics a = s[M-1] and b = s[K] of every column are selected without a sort, per window the values < a and > b are
+ * compacted into two buffers of M (open slots take the threshold: equal doubles), and only these 2 x columns segments of M
+ * are sorted.  Path rule, from the shape and the windows alone: tails when N >= 4096 and every window has 8 * M <= N (and
+ * 2 * columns * max M < 2^31), else full; the environment variable BISIP_HDI_PATH=full|tails, read on every call by both
+ * functions, forces one.  Measured on an MI355X (benchmarks/interval_bench.py, medians of 5, the
+ * paths alternating; profiles/r05_interval_bench.jsonl): 512 ensembles x 128,000 values x 7, mass 0.95 (M = N / 20): tails
+ * 8.0 ms, full 34.6 ms (the parent's gather + sort of everything: 31.0 ms); masses (0.5, 0.9, 0.95) in one call (M = N / 2, N /
+ * 10, N / 20): tails 50.0 ms, full 35.5 ms; seven columns of 160,000: 0.51 against 5.4 ms, and 4.1 against 5.5 ms.  The rule
+ * lies between the two measured points, on the safe side: the tails never run where they were measured slower.
+ * d_work: bisip_chain_hdi_workspace() BYTES (< 0: shape or windows refused; more than 2^31 values: the sort's limit), with
+ * c = align256(8 * N * columns), columns = n_ensembles * ndim, t = align256(8 * 2 * columns * max M):
+ *   full: 2 c + scratch(N * columns, columns);  tails: c + align256(16 * n_windows * columns) + align256(8 * columns) +
+ *   align256(4 * columns) + 2 t + scratch(2 * columns * max M, 2 * columns); scratch(items, segments) = align256(align256(8 *
+ *   items) + 16 * segments + 65536), a bound on what the library's segmented sort asks for (BISIP_EUNSUPPORTED if it ever
+ *   asks for more): the workspace is sized without a device.
+ * Asynchronous on stream, no host synchronisation. */
+int64_t bisip_chain_hdi_workspace(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim,
+                                  int n_windows, const int64_t *windows);
+int bisip_chain_hdi_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+                        int64_t walkers_per_ensemble, int ndim, const int64_t *windows, int n_windows, double *d_out,
+                        int64_t *d_index, void *d_work, int64_t work_bytes, void *stream);
+
 /* np.percentile(rows, p, axis=0) for a device-resident (n_rows, n_cols) array (linear rule):
  * d_out (n_percentiles, n_cols).  Workspace in BYTES (0: more than 2^31 values). */
 int64_t bisip_column_percentiles_workspace(int64_t n_rows, int n_cols, int n_percentiles);
