@@ -1,0 +1,62 @@
+// chain.h -- what the chain_*.hip units share: the error plumbing, the column toolkit and the one segmented sort
+// (both in chain_columns.hip), and the launch of a kernel that is a template of ndim.  A unit that summarises a
+// device-resident chain includes this header and nothing of the samplers' (host.h, kernels.h).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "../../include/bisip_hip.h"
+#include "errors.h"
+
+namespace bisip {
+namespace host {
+
+// the column toolkit: what the percentile entry points share with chain_trace.hip and chain_hdi.hip
+int percentile_ranks(long long n, const double *percentiles, int n_percentiles, std::vector<long long> &lo, std::vector<double> &t);
+int select_columns(const double *cols, long long n, long long columns, int n_percentiles, const std::vector<long long> &lo,
+                   const std::vector<double> &t, double *d_out, hipStream_t st, long long out_stride = 0, bool raw = false);
+int gather_columns(const double *d_chain, long long n_samples, long long sample_stride, long long E, long long Wp, int ndim,
+                   double *cols, hipStream_t st);
+int gather_columns_by_sample(const double *d_chain, long long n_samples, long long sample_stride, long long E, long long Wp,
+                             int ndim, double *cols, hipStream_t st);
+
+// the segmented radix sort of `segments` contiguous segments of n doubles each (items = segments * n < 2^31)
+size_t align256(size_t x);
+int sort_temp_bytes(long long items, long long segments, long long n, size_t *bytes);
+size_t sort_scratch_bound(long long items, long long segments);
+int sort_segments(void *d_temp, size_t temp, const double *in, double *out, long long items, long long segments, long long n,
+                  hipStream_t st);
+
+// Launch<ndim>::run(grid, st, args) for a kernel that is a template of ndim (chain_rtd.hip, chain_hist.hip)
+template <template <int> class Launch, typename Args>
+int launch_by_ndim(int ndim, dim3 grid, hipStream_t st, const Args &args)
+{
+    switch (ndim) {
+    case 2: Launch<2>::run(grid, st, args); break;
+    case 3: Launch<3>::run(grid, st, args); break;
+    case 4: Launch<4>::run(grid, st, args); break;
+    case 5: Launch<5>::run(grid, st, args); break;
+    case 6: Launch<6>::run(grid, st, args); break;
+    case 7: Launch<7>::run(grid, st, args); break;
+    case 8: Launch<8>::run(grid, st, args); break;
+    case 9: Launch<9>::run(grid, st, args); break;
+    case 10: Launch<10>::run(grid, st, args); break;
+    case 11: Launch<11>::run(grid, st, args); break;
+    case 12: Launch<12>::run(grid, st, args); break;
+    case 13: Launch<13>::run(grid, st, args); break;
+    case 14: Launch<14>::run(grid, st, args); break;
+    case 15: Launch<15>::run(grid, st, args); break;
+    case 16: Launch<16>::run(grid, st, args); break;
+    default: return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
+    }
+    HIP_TRY(hipGetLastError());
+    return BISIP_OK;
+}
+static_assert(BISIP_MAX_NDIM == 16, "launch_by_ndim covers ndim 2 ... 16");
+
+}  // namespace host
+}  // namespace bisip

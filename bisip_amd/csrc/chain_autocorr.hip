@@ -18,7 +18,7 @@
 // Rounds are enqueued without a host synchronisation.  An (e, d) whose window is found is marked done;
 // tiles whose series are all done leave the later rounds at once.  No floating-point atomics: the same
 // chain gives the same bits every call.
-#include "host.h"
+#include "chain.h"
 
 using namespace bisip;
 using namespace bisip::host;
@@ -223,8 +223,6 @@ __global__ __launch_bounds__(64) void k_ac_window(const AcArgs a, const double *
         if (stop) return;
     }
 }
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // lags per round: enough lag workgroups to fill the chip next to the tiles, no more than the chain has
 long long round_lags(long long n_t, long long M)

@@ -34,7 +34,7 @@
 // ndim doubles are copied as they are.
 #include <climits>
 
-#include "host.h"
+#include "chain.h"
 
 using namespace bisip;
 using namespace bisip::host;

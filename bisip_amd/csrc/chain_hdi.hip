@@ -6,7 +6,7 @@
 // (include/bisip_hip.h; bisip_amd/interval.py holds the definition in NumPy).  Subtractions and comparisons of the same
 // doubles: the result equals the definition's, bit for bit (up to the sign of a zero).
 //
-//   full path:  gather the columns (chain_stats.hip: gather_columns), sort them all with the segmented radix sort,
+//   full path:  gather the columns (chain_columns.hip: gather_columns), sort them all with the segmented radix sort,
 //               k_hdi_window over L = s, U = s + K.
 //   tails path: only L = s[0 .. M-1] and U = s[K .. N-1] are ever read.  The order statistics a = s[M-1] and b = s[K] of
 //               every column come from the selection kernel (select_columns, raw output); per window k_tails_compact
@@ -14,9 +14,7 @@
 //               threshold itself (equal doubles are interchangeable), the segmented sort orders the 2 x columns segments
 //               of M and k_hdi_window reads the pairs.
 // The path is a function of the shape and the windows alone (hdi_path below); BISIP_HDI_PATH=full|tails forces one.
-#include "host.h"
-
-#include <hipcub/hipcub.hpp>
+#include "chain.h"
 
 #include <cstdlib>
 
@@ -164,46 +162,6 @@ __global__ __launch_bounds__(HDI_THREADS) void k_tails_fill(const TailsArgs a)
     if (idx >= 2 * a.columns * a.M) return;
     const long long seg = idx / a.M, j = idx - seg * a.M;
     if (j >= (long long)a.count[seg]) a.tails[idx] = seg < a.columns ? a.thr_a[seg] : a.thr_b[seg - a.columns];
-}
-
-struct SegmentOffset {
-    long long n;
-    __host__ __device__ int operator()(int i) const { return (int)(i * n); }
-};
-using Counting = hipcub::CountingInputIterator<int>;
-using Offsets = hipcub::TransformInputIterator<int, SegmentOffset, Counting>;
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-int sort_temp_bytes(long long items, long long segments, long long n, size_t *bytes)
-{
-    Offsets begin(Counting(0), SegmentOffset{n}), end(Counting(1), SegmentOffset{n});
-    size_t temp = 0;
-    hipError_t e = hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, temp, (const double *)nullptr, (double *)nullptr,
-                                                              (int)items, (int)segments, begin, end);
-    if (e != hipSuccess) return fail(BISIP_EHIP, "segmented sort sizing failed: %s", hipGetErrorString(e));
-    *bytes = temp;
-    return BISIP_OK;
-}
-
-// What the workspace reserves for the sort's scratch: a second copy of the keys, two index lists of the segments and the
-// state of their partition (rocPRIM's segmented radix sort), with room to spare -- a formula, so that the workspace can be
-// sized without a device.  sort_segments refuses a sort that asks for more.
-size_t sort_scratch_bound(long long items, long long segments)
-{
-    return align256((size_t)items * 8) + (size_t)segments * 16 + 65536;
-}
-
-int sort_segments(void *d_temp, size_t temp, const double *in, double *out, long long items, long long segments, long long n,
-                  hipStream_t st)
-{
-    size_t asked = 0;
-    int rc = sort_temp_bytes(items, segments, n, &asked);
-    if (rc != BISIP_OK) return rc;
-    if (asked > temp) return fail(BISIP_EUNSUPPORTED, "the segmented sort asks for %zu bytes of scratch, %zu reserved", asked, temp);
-    Offsets begin(Counting(0), SegmentOffset{n}), end(Counting(1), SegmentOffset{n});
-    HIP_TRY(hipcub::DeviceSegmentedRadixSort::SortKeys(d_temp, temp, in, out, (int)items, (int)segments, begin, end, 0, 64, st));
-    return BISIP_OK;
 }
 
 enum HdiPath { HDI_FULL = 0, HDI_TAILS = 1 };

@@ -27,7 +27,7 @@
 // workgroup per ensemble that keeps the chain moments in LDS: no workspace.  Everything else: k_rhat_accumulate (a lane
 // per (half, segment, column); with one segment it finishes the moments itself), k_rhat_merge when there are several
 // segments, k_rhat_stage (a workgroup per ensemble, a wave per parameter).  The arithmetic is the same functions in both.
-#include "host.h"
+#include "chain.h"
 
 using namespace bisip;
 using namespace bisip::host;

@@ -16,7 +16,7 @@
 // split over enough workgroups to fill the chip, histograms meet in global memory, and the levels are separate
 // launches (hist, hist, compact; every workgroup derives the threshold digits from the finished histograms
 // itself).  HBM-bound: 8 B per stored sample and sweep, four loads in flight per lane.
-#include "host.h"
+#include "chain.h"
 
 using namespace bisip;
 using namespace bisip::host;

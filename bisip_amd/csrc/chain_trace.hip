@@ -18,7 +18,7 @@
 //   * Ensembles beyond bisip_chain_trace_lds_walkers(ndim) go slab by slab through k_gather_columns_tiled (one column
 //     per (sample, ensemble, parameter)), k_segmented_select and k_trace_column_mean: the same order statistics, the
 //     same _lerp, the same summation order => the same doubles whichever path ran.
-#include "host.h"
+#include "chain.h"
 #include "select_key.h"
 
 using namespace bisip;

@@ -13,22 +13,13 @@
 #include <vector>
 
 #include "../../include/bisip_hip.h"
+#include "errors.h"
 #include "host_precompute.h"
 #include "kernels.h"
 #include "sampler_kernels.h"
 
 namespace bisip {
 namespace host {
-
-int fail(int code, const char *fmt, ...);
-
-#define HIP_TRY(expr)                                                                  \
-    do {                                                                               \
-        hipError_t e_ = (expr);                                                        \
-        if (e_ != hipSuccess)                                                          \
-            return ::bisip::host::fail(BISIP_EHIP, "%s failed: %s (%s:%d)", #expr,     \
-                                       hipGetErrorString(e_), __FILE__, __LINE__);     \
-    } while (0)
 
 constexpr int BLK_SMALL = 64;    // few walkers: spread them over more CUs
 constexpr int BLK_LARGE = 256;
@@ -174,15 +165,6 @@ StretchArgs to_device_args(const bisip_stretch_args *u);
 int dispatch_stretch(const bisip_ctx *c, const StretchWork &a, long long Wp, hipStream_t st);
 int dispatch_stretch_batch(const bisip_ctx *c, const StretchWork &a, long long Wp, hipStream_t st);   // dispatch_stretch_batch.hip
 int dispatch_apply(const bisip_ctx *c, const StretchArgs &a, hipStream_t st);
-
-// chain_stats.hip: what the percentile entry points share with chain_trace.hip and chain_hdi.hip
-int percentile_ranks(long long n, const double *percentiles, int n_percentiles, std::vector<long long> &lo, std::vector<double> &t);
-int select_columns(const double *cols, long long n, long long columns, int n_percentiles, const std::vector<long long> &lo,
-                   const std::vector<double> &t, double *d_out, hipStream_t st, long long out_stride = 0, bool raw = false);
-int gather_columns(const double *d_chain, long long n_samples, long long sample_stride, long long E, long long Wp, int ndim,
-                   double *cols, hipStream_t st);
-int gather_columns_by_sample(const double *d_chain, long long n_samples, long long sample_stride, long long E, long long Wp,
-                             int ndim, double *cols, hipStream_t st);
 
 }  // namespace host
 }  // namespace bisip

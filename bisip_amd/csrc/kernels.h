@@ -2071,7 +2071,7 @@ __global__ __launch_bounds__(64) void k_forward_tiled16(const LaunchArgs a)
 }
 
 // forward() written COLUMN-major: out (spectra, 2N, Wp) -- one contiguous column per (spectrum, part, frequency).
-// What the percentile kernels read (chain_stats.hip), so the model-space bands of a survey need no
+// What the percentile kernels read (chain_columns.hip), so the model-space bands of a survey need no
 // row -> column transposition (a 27 GB round trip for 4096 spectra): lane = walker, every store instruction
 // writes 64 consecutive doubles of one column, no LDS staging needed.  Same M::eval, same values as Z.
 // PA (BISIP_RESPONSE_PA): column j holds the amplitude hypot(re, im) and column N + j MINUS the phase, -atan2(im, re), in

@@ -1,5 +1,5 @@
 // select_key.h -- the order-preserving 64-bit image of a double that the selection kernels compare
-// (chain_stats.hip: k_segmented_select, k_chain_range; chain_trace.hip: k_chain_trace_lds).
+// (chain_columns.hip: k_segmented_select; chain_hist.hip: k_chain_range; chain_trace.hip: k_chain_trace_lds).
 #pragma once
 #include <hip/hip_runtime.h>
 
