@@ -141,6 +141,15 @@ SYMBOLS = {
     'bisip_chain_hdi_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                            ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    'bisip_chain_ess_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_int]),
+    'bisip_chain_ess_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    'bisip_chain_rank_normalize_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    'bisip_chain_rank_normalize_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                      ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_int64, ctypes.c_void_p]),
     'bisip_column_percentiles_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     'bisip_column_percentiles_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, _dp, ctypes.c_int,
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
@@ -944,6 +953,38 @@ def chain_hdi_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_pe
     _check(load_library().bisip_chain_hdi_dev(d_chain_ptr or None, int(n_samples), int(sample_stride), int(n_ensembles),
                                               int(walkers_per_ensemble), int(ndim), w, nw, d_out_ptr or None,
                                               d_index_ptr or None, d_work_ptr or None, int(work_bytes), stream))
+
+
+def chain_ess_workspace(n_samples, n_ensembles, walkers_per_ensemble, ndim, splits, n_threshold=0):
+    """Bytes of device scratch chain_ess_dev needs (0: shape not supported)."""
+    return int(load_library().bisip_chain_ess_workspace(int(n_samples), int(n_ensembles), int(walkers_per_ensemble), int(ndim),
+                                                        int(splits), int(n_threshold)))
+
+
+def chain_ess_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, splits, d_threshold_ptr,
+                  n_threshold, d_ess_ptr, d_work_ptr=0, work_bytes=0, stream=0):
+    """The effective sample size of every (ensemble, parameter) over its walkers' series, or their two halves (``splits``
+    = 1 / 2), into d_ess (n_ensembles, ndim); with d_threshold (n_threshold, n_ensembles, ndim) of the indicators ``x <=
+    threshold`` instead, into d_ess (n_threshold, n_ensembles, ndim).  Device pointers (ints), asynchronous on ``stream``."""
+    _check(load_library().bisip_chain_ess_dev(d_chain_ptr or None, int(n_samples), int(sample_stride), int(n_ensembles),
+                                              int(walkers_per_ensemble), int(ndim), int(splits), d_threshold_ptr or None,
+                                              int(n_threshold), d_ess_ptr or None, d_work_ptr or None, int(work_bytes),
+                                              stream))
+
+
+def chain_rank_normalize_workspace(n_samples, n_ensembles, walkers_per_ensemble, ndim):
+    """Bytes of device scratch chain_rank_normalize_dev needs (0: shape not supported, more than 2^31 values)."""
+    return int(load_library().bisip_chain_rank_normalize_workspace(int(n_samples), int(n_ensembles),
+                                                                   int(walkers_per_ensemble), int(ndim)))
+
+
+def chain_rank_normalize_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, d_z_ptr,
+                             d_work_ptr=0, work_bytes=0, stream=0):
+    """The rank-normalised chain (bisip_amd.ess.z_scale per ensemble) into d_z (n_samples, n_ensembles *
+    walkers_per_ensemble, ndim), contiguous.  Device pointers (ints), asynchronous on ``stream``."""
+    _check(load_library().bisip_chain_rank_normalize_dev(d_chain_ptr or None, int(n_samples), int(sample_stride),
+                                                         int(n_ensembles), int(walkers_per_ensemble), int(ndim),
+                                                         d_z_ptr or None, d_work_ptr or None, int(work_bytes), stream))
 
 
 def ensemble_gram_workspace(W, ndim):

@@ -12,6 +12,7 @@ import numpy as np
 from . import _hip, decomposition
 from .autocorr import AutocorrError
 from .covariance import BatchCovariance
+from .ess import BatchEss
 from .interval import BatchIntervals
 from .dist import shard_range
 from .response import BatchResponse
@@ -49,7 +50,7 @@ def default_params(model, n_modes=1, poly_deg=5):
     return p
 
 
-class SpectraBatch(BatchCovariance, BatchIntervals, BatchResponse):
+class SpectraBatch(BatchCovariance, BatchIntervals, BatchEss, BatchResponse):
     """E spectra inverted together with the same model class.
 
     Args:

@@ -3,7 +3,7 @@
 ``DeviceChainSummaries`` is the part of ``DeviceEnsembleSampler`` that has nothing to do with sampling: it finds the
 used samples of the stored chain (or log-probability) on the device as a ChainView and hands that to the ``device_*``
 function of the family asked for (bisip_amd.chainview, .autocorr, .histogram, .trace, .convergence, .covariance,
-.interval, .decomposition, .response).
+.interval, .ess, .decomposition, .response).
 ``device_model_percentiles`` also needs the model: forward over the samples, then the order statistics of each response.
 """
 
@@ -15,6 +15,7 @@ from .autocorr import check_c, check_tol, device_integrated_time
 from .chainview import ChainView, _merge_device_parts, device_moments, device_percentiles, used_range
 from .convergence import device_rhat
 from .covariance import corr_from_cov, device_best_sample, device_cov
+from .ess import device_ess, device_mcse_mean
 from .interval import device_hdi
 from .response import device_model_moments
 from .trace import device_trace
@@ -189,6 +190,23 @@ class DeviceChainSummaries:
     def log_prob_rhat(self, discard=0, thin=1, split=True):
         """R-hat of every ensemble's stored log-probability, ``(n_ensembles,)``, on the device."""
         return device_rhat(self.log_prob_samples_dev(discard, thin), split=split)[:, 0]
+
+    def param_ess(self, kind='bulk', discard=0, thin=1, split=True):
+        """The effective sample size (``kind``: 'bulk', 'tail' or 'mean'; bisip_amd.ess) of every parameter of every
+        ensemble over its walkers' series of ``get_chain(discard, thin)``, each cut into halves unless ``split=False``:
+        ``(n_ensembles, ndim)``, taken on the device (bisip_chain_ess_dev, bisip_chain_rank_normalize_dev) from the chain
+        where it lies (``chain_on_device``), else from an upload of the used samples only.  Walkers of an ensemble are not
+        independent chains: the between-walker term is a screening device."""
+        return device_ess(self.used_samples_dev(discard, thin), kind, split)
+
+    def log_prob_ess(self, kind='bulk', discard=0, thin=1, split=True):
+        """The effective sample size of every ensemble's stored log-probability, ``(n_ensembles,)``, on the device."""
+        return device_ess(self.log_prob_samples_dev(discard, thin), kind, split)[:, 0]
+
+    def param_mcse_mean(self, discard=0, thin=1):
+        """The Monte-Carlo standard error of every posterior mean, ``(n_ensembles, ndim)``: param_moments' standard
+        deviation times ``sqrt(N / (N - 1))`` over the square root of the 'mean' effective sample size."""
+        return device_mcse_mean(self.used_samples_dev(discard, thin))
 
     def param_cov(self, discard=0, thin=1):
         """``np.cov`` (ddof = 1) of every ensemble's used samples flattened over its walkers -- of ``get_chain(discard,

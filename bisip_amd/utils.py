@@ -14,6 +14,7 @@ import numpy as np
 
 from .chainview import used_range
 from .covariance import ModelCovariance
+from .ess import ModelEss
 from .interval import ModelIntervals
 from .response import ModelResponse
 
@@ -182,11 +183,11 @@ def refuse_discard_of_a_chain(kwargs):
                          'thin keywords to parse the full chain. Do not pass both.')
 
 
-class utils(ModelCovariance, ModelIntervals, ModelResponse):
+class utils(ModelCovariance, ModelIntervals, ModelEss, ModelResponse):
     """Mixin with the reference's utility methods (src/bisip/utils.py:15); the posterior covariance, correlation and best
     sample come from bisip_amd.covariance.ModelCovariance, the highest-density intervals from
-    bisip_amd.interval.ModelIntervals, the amplitude / phase bands and the moments of the model
-    response from bisip_amd.response.ModelResponse."""
+    bisip_amd.interval.ModelIntervals, the effective sample sizes from bisip_amd.ess.ModelEss, the amplitude / phase
+    bands and the moments of the model response from bisip_amd.response.ModelResponse."""
 
     def load_data(self, filename, headers=1, ph_units='mrad'):
         return load_data(filename, headers, ph_units)

@@ -538,6 +538,56 @@ int bisip_chain_hdi_dev(const double *d_chain, int64_t n_samples, int64_t sample
                         int64_t walkers_per_ensemble, int ndim, const int64_t *windows, int n_windows, double *d_out,
                         int64_t *d_index, void *d_work, int64_t work_bytes, void *stream);
 
+/* Effective sample size of every (ensemble, parameter) of a chain resident in device memory: the estimator of Vehtari,
+ * Gelman, Simpson, Carpenter and Buerkner (2021) as Stan and ArviZ compute it (bisip_amd/ess.py holds the definition in
+ * NumPy: ess_of_chains).  Walkers of an ensemble sampler are not independent chains: the between-chain term is a
+ * screening device, as R-hat is.  Chain layout, d_chain / sample_stride conventions as for bisip_chain_moments_dev
+ * (discard: an offset, thin: a stride, padding allowed); ndim 1 ... BISIP_MAX_NDIM (ndim = 1: a stored log-probability).
+ * splits = 1: a chain is a walker's whole series, L = n_samples; splits = 2: its first and its last L = n_samples / 2
+ * samples are two chains (the middle sample of an odd n_samples is in neither).  M = splits * walkers_per_ensemble chains
+ * c = half * walkers_per_ensemble + w, S = L * M.  BISIP_EINVAL when n_samples < 2 * splits.
+ *   d_threshold == NULL (n_threshold = 0): the series are the values; d_ess (n_ensembles, ndim).
+ *   d_threshold (n_threshold, n_ensembles, ndim), 1 <= n_threshold <= 8: the series are the indicators x <= thr ? 1.0 :
+ *     0.0, taken on load; d_ess (n_threshold, n_ensembles, ndim).  A NaN threshold gives NaN.
+ *   Per (threshold, ensemble, parameter): NaN when a value of its chains is not finite; S when max - min < 1e-15; else with
+ *   y = series - its chain's mean (the mean from sums shifted by the chain's first sample: a constant chain is centred to
+ *   exact zeros), abar_k = sum over the chains of sum_{t < L - k} y_t y_{t + k} (pairs inside the half, fma), / L / M;
+ *   mean_var = abar_0 L / (L - 1); var_plus = abar_0 + the variance (ddof = 1, two passes) of the chain means when M > 1;
+ *   rho_k = 1 - (mean_var - abar_k) / var_plus; Geyer's initial positive sequence over pairs (rho_{t+1}, rho_{t+2}), t = 1,
+ *   3, ... while t < L - 3 and the pair consumed last sums to > 0; the initial monotone sequence (a pair whose sum
+ *   exceeds its predecessor's becomes twice that one's mean) and tau = -1 + 2 sum_{k <= max_t} rho_k + rho_{max_t + 1}
+ *   are taken pair by pair on the way, so no rho is stored; tau >= 1 / log10(S); ESS = S / tau.
+ * Work: the lag sums go in rounds of Lr = 64 * min(ceil(L / 64), max(1, ceil(512 / (tiles * n_series)))) lags, tiles =
+ * ceil(C / 64), C = n_ensembles * walkers_per_ensemble * ndim, n_series = max(1, n_threshold) * splits: (tile of 64 series)
+ * x (block of 64 lags) workgroups, the centred samples through LDS, 16 lag accumulators per lane; the round's sums are
+ * added over the chains in groups of 256, groups in ascending order; one wave per (threshold, ensemble, parameter)
+ * continues the sequence and marks it done when it ends; tiles whose sequences are all done leave later rounds at once.
+ * d_work: bisip_chain_ess_workspace() BYTES (0: shape not supported): three doubles per series, Lr doubles per series
+ * and per (pair, chain group), the scan's state.  The plan depends on the shape alone.  No floating-point atomics: the
+ * same bits on every call.  64-bit offsets.  Asynchronous on stream, no host synchronisation between rounds. */
+int64_t bisip_chain_ess_workspace(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim,
+                                  int splits, int n_threshold);
+int bisip_chain_ess_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+                        int64_t walkers_per_ensemble, int ndim, int splits, const double *d_threshold, int n_threshold,
+                        double *d_ess, void *d_work, int64_t work_bytes, void *stream);
+
+/* Rank-normalisation of a chain resident in device memory, what the bulk effective sample size is taken of
+ * (bisip_amd/ess.py: z_scale).  Chain layout, d_chain / sample_stride conventions as above.  Per (ensemble, parameter)
+ * the N = n_samples * walkers_per_ensemble values are ranked from 1, ties sharing the mean of their ranks (-0.0 and 0.0
+ * are equal), and z = ndtri((r - 3 / 8) / (N + 1 / 4)) with Wichura's AS 241 routine PPND16 in double, in the order of
+ * operations of the definition.  d_z (n_samples, n_ensembles * walkers_per_ensemble, ndim), contiguous, in the order of
+ * the chain.  A value that is not finite makes every z of its (ensemble, parameter) NaN and no other.
+ * The columns are gathered and sorted (the library's segmented radix sort: n_ensembles * N * ndim < 2^31 values, else
+ * BISIP_EUNSUPPORTED -- the caller goes in passes of ensembles), then one thread per chain element finds, by two binary
+ * searches of its sorted column, how many values are smaller and how many are not larger: no index goes through the sort.
+ * d_work: bisip_chain_rank_normalize_workspace() BYTES (0: shape not supported) = 2 align256(8 * items) +
+ * scratch(items, n_ensembles * ndim), items = n_ensembles * N * ndim, scratch as for bisip_chain_hdi_workspace.
+ * Asynchronous on stream, no host synchronisation. */
+int64_t bisip_chain_rank_normalize_workspace(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim);
+int bisip_chain_rank_normalize_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+                                   int64_t walkers_per_ensemble, int ndim, double *d_z, void *d_work, int64_t work_bytes,
+                                   void *stream);
+
 /* np.percentile(rows, p, axis=0) for a device-resident (n_rows, n_cols) array (linear rule):
  * d_out (n_percentiles, n_cols).  Workspace in BYTES (0: more than 2^31 values). */
 int64_t bisip_column_percentiles_workspace(int64_t n_rows, int n_cols, int n_percentiles);
