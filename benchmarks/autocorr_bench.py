@@ -33,7 +33,7 @@ SHAPES = {   # name: (E, Wp, ndim, stored, discard)
     'big_131072x200': (1, 131072, 7, 200, 0),
 }
 HBM_PEAK = 8.0e12          # bytes/s, MI355X spec
-TILE, LAG_BLOCK, T_STAGE, TARGET_BLOCKS = 64, 64, 32, 512    # chain_autocorr.hip
+TILE, LAG_BLOCK, T_STAGE, TARGET_BLOCKS = 64, 64, 32, 512    # bisip_amd/csrc/chain_lags.h
 
 
 def make_chain(E, Wp, ndim, n, seed=0):

@@ -1,6 +1,7 @@
-// chain.h -- what the chain_*.hip units share: the error plumbing, the column toolkit and the one segmented sort
-// (both in chain_columns.hip), and the launch of a kernel that is a template of ndim.  A unit that summarises a
-// device-resident chain includes this header and nothing of the samplers' (host.h, kernels.h).
+// chain.h -- what the chain_*.hip units share: the error plumbing, the sum over a wave, the column toolkit and the one
+// segmented sort (both in chain_columns.hip), and the launch of a kernel that is a template of ndim.  A unit that
+// summarises a device-resident chain includes this header and nothing of the samplers' (host.h, kernels.h); the two
+// units that take lag sums include it through chain_lags.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +14,15 @@
 #include "errors.h"
 
 namespace bisip {
+
+// the sum of x over the 64 lanes of a wave, in every lane: lanes 32, 16, ..., 1 apart are added pairwise
+__device__ __forceinline__ double wave_sum(double x)
+{
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) x += __shfl_xor(x, s, 64);
+    return x;
+}
+
 namespace host {
 
 // the column toolkit: what the percentile entry points share with chain_trace.hip and chain_hdi.hip

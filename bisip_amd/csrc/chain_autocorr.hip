@@ -9,30 +9,20 @@
 // lag where k < c*taus_k turns false (emcee's auto_window).  Three kernels:
 //   1. k_ac_prep: mean and acf_0 of every series; one workgroup per tile of 64 series, the samples split
 //      over its 16 waves and the partial sums added in a fixed order;
-//   2. k_ac_lags: a round of L lags: (tile of 64 series) x (block of 64 lags); the centred samples of the
-//      tile go through LDS, every lane keeps 16 lag accumulators in registers; writes acf_k / acf_0 for the
-//      round's lags into the workspace (L per series);
+//   2. k_ac_lags: a round of L lags on the lag-sum tile of chain_lags.h; writes acf_k / acf_0 for the round's
+//      lags into the workspace (L per series);
 //   3. k_ac_walker_sums + k_ac_window: the round's normalised lags summed over the walkers of every
 //      (ensemble, parameter) -- lanes over lags, groups of 256 walkers in order, then the groups in order --
 //      and one wave per (ensemble, parameter) continues the cumulative sum and tests the window.
 // Rounds are enqueued without a host synchronisation.  An (e, d) whose window is found is marked done;
 // tiles whose series are all done leave the later rounds at once.  No floating-point atomics: the same
 // chain gives the same bits every call.
-#include "chain.h"
+#include "chain_lags.h"
 
 using namespace bisip;
 using namespace bisip::host;
 
 namespace {
-
-constexpr int AC_TILE = 64;        // series per tile (one per lane)
-constexpr int AC_LAGS_WAVE = 16;   // lag accumulators per lane
-constexpr int AC_WAVES = 4;        // waves of a lag workgroup
-constexpr int AC_LAG_BLOCK = AC_LAGS_WAVE * AC_WAVES;   // lags per lag workgroup
-constexpr int AC_T = 32;           // samples staged per pass
-constexpr int AC_TARGET_BLOCKS = 512;                   // two lag workgroups per compute unit
-constexpr int AC_PREP_WAVES = 16;
-constexpr int AC_WALKERS_GROUP = 256;                  // walkers one k_ac_walker_sums workgroup adds
 
 struct AcArgs {
     const double *chain;
@@ -57,29 +47,29 @@ __global__ __launch_bounds__(256) void k_ac_init(const AcArgs a)
 }
 
 // mean and sum of centred squares of 64 series; wave q takes samples q, q + 16, ...
-__global__ __launch_bounds__(AC_PREP_WAVES * 64) void k_ac_prep(const AcArgs a, double *mean, double *a0)
+__global__ __launch_bounds__(LAG_PREP_WAVES * 64) void k_ac_prep(const AcArgs a, double *mean, double *a0)
 {
-    __shared__ double part[AC_PREP_WAVES][AC_TILE];
-    __shared__ double mu[AC_TILE];
+    __shared__ double part[LAG_PREP_WAVES][LAG_TILE];
+    __shared__ double mu[LAG_TILE];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long j = (long long)blockIdx.x * AC_TILE + lane;
+    const long long j = (long long)blockIdx.x * LAG_TILE + lane;
     const bool live = j < a.M;
     const double *x = a.chain + (live ? j : 0);
     double s = 0.0;
     if (live)
-        for (long long t = wave; t < a.n_t; t += AC_PREP_WAVES) s += x[t * a.stride];
+        for (long long t = wave; t < a.n_t; t += LAG_PREP_WAVES) s += x[t * a.stride];
     part[wave][lane] = s;
     __syncthreads();
     if (wave == 0) {
         double tot = 0.0;
-        for (int q = 0; q < AC_PREP_WAVES; ++q) tot += part[q][lane];
+        for (int q = 0; q < LAG_PREP_WAVES; ++q) tot += part[q][lane];
         mu[lane] = tot / (double)a.n_t;
     }
     __syncthreads();
     const double m = mu[lane];
     s = 0.0;
     if (live)
-        for (long long t = wave; t < a.n_t; t += AC_PREP_WAVES) {
+        for (long long t = wave; t < a.n_t; t += LAG_PREP_WAVES) {
             const double y = x[t * a.stride] - m;
             s = fma(y, y, s);
         }
@@ -87,24 +77,22 @@ __global__ __launch_bounds__(AC_PREP_WAVES * 64) void k_ac_prep(const AcArgs a, 
     __syncthreads();
     if (wave == 0 && live) {
         double tot = 0.0;
-        for (int q = 0; q < AC_PREP_WAVES; ++q) tot += part[q][lane];
+        for (int q = 0; q < LAG_PREP_WAVES; ++q) tot += part[q][lane];
         mean[j] = m;
         a0[j] = tot;
     }
 }
 
-// One round's lags [k0, k0 + L) of 64 series.  Workgroup (tile, b) owns lags kb = k0 + 64 b ... kb + 63,
-// wave w the 16 lags kb + 16 w + i.  acc_i = sum_t y_t y_{t + kb + 16 w + i} over t < n_t - kb, with y = 0
-// beyond the chain (a zero product adds nothing).  Per pass the LDS holds y[t0, t0 + 32) (A) and
-// y[t0 + kb, t0 + kb + 96) (B) of the tile, one lane's series per column.
-__global__ __launch_bounds__(AC_WAVES * 64) void k_ac_lags(const AcArgs a)
+// One round's lags [k0, k0 + L) of 64 series: workgroup (tile, b) takes the lag sums of lags kb = k0 + 64 b ... kb + 63
+// over the n_t samples on the tile of chain_lags.h (the loop is k_ess_lags' of chain_ess.hip) and stores them over acf_0.
+__global__ __launch_bounds__(LAG_WAVES * 64) void k_ac_lags(const AcArgs a)
 {
-    __shared__ double A[AC_T][AC_TILE];
-    __shared__ double B[AC_T + AC_LAG_BLOCK][AC_TILE];
+    __shared__ double A[LAG_T][LAG_TILE];
+    __shared__ double B[LAG_T + LAG_BLOCK][LAG_TILE];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long kb = a.k0 + (long long)blockIdx.y * AC_LAG_BLOCK;
+    const long long kb = a.k0 + (long long)blockIdx.y * LAG_BLOCK;
     if (kb >= a.n_t) return;
-    const long long j = (long long)blockIdx.x * AC_TILE + lane;
+    const long long j = (long long)blockIdx.x * LAG_TILE + lane;
     const bool live = j < a.M;
     // the tile leaves when every series in it belongs to an (e, d) whose window is known
     // (the same 64 lanes in every wave: the exit is uniform over the workgroup)
@@ -119,41 +107,41 @@ __global__ __launch_bounds__(AC_WAVES * 64) void k_ac_lags(const AcArgs a)
     const double *x = a.chain + (live ? j : 0);
     auto y = [&](long long t) { return live && t < a.n_t ? x[t * a.stride] - m : 0.0; };
 
-    double acc[AC_LAGS_WAVE];
+    double acc[LAGS_WAVE];
 #pragma unroll
-    for (int i = 0; i < AC_LAGS_WAVE; ++i) acc[i] = 0.0;
+    for (int i = 0; i < LAGS_WAVE; ++i) acc[i] = 0.0;
     const long long t_end = a.n_t - kb;     // samples that still meet a partner at lag kb
-    for (long long t0 = 0; t0 < t_end; t0 += AC_T) {
+    for (long long t0 = 0; t0 < t_end; t0 += LAG_T) {
         __syncthreads();                    // the previous pass has read A and B
-        for (int r = wave; r < AC_T; r += AC_WAVES) A[r][lane] = y(t0 + r);
-        for (int r = wave; r < AC_T + AC_LAG_BLOCK; r += AC_WAVES) B[r][lane] = y(t0 + kb + r);
+        for (int r = wave; r < LAG_T; r += LAG_WAVES) A[r][lane] = y(t0 + r);
+        for (int r = wave; r < LAG_T + LAG_BLOCK; r += LAG_WAVES) B[r][lane] = y(t0 + kb + r);
         __syncthreads();
 #pragma unroll
-        for (int sc = 0; sc < AC_T; sc += AC_LAGS_WAVE) {
-            double av[AC_LAGS_WAVE], bv[2 * AC_LAGS_WAVE];
+        for (int sc = 0; sc < LAG_T; sc += LAGS_WAVE) {
+            double av[LAGS_WAVE], bv[2 * LAGS_WAVE];
 #pragma unroll
-            for (int s = 0; s < AC_LAGS_WAVE; ++s) av[s] = A[sc + s][lane];
+            for (int s = 0; s < LAGS_WAVE; ++s) av[s] = A[sc + s][lane];
 #pragma unroll
-            for (int q = 0; q < 2 * AC_LAGS_WAVE; ++q) bv[q] = B[sc + AC_LAGS_WAVE * wave + q][lane];
+            for (int q = 0; q < 2 * LAGS_WAVE; ++q) bv[q] = B[sc + LAGS_WAVE * wave + q][lane];
 #pragma unroll
-            for (int s = 0; s < AC_LAGS_WAVE; ++s)
+            for (int s = 0; s < LAGS_WAVE; ++s)
 #pragma unroll
-                for (int i = 0; i < AC_LAGS_WAVE; ++i) acc[i] = fma(av[s], bv[s + i], acc[i]);
+                for (int i = 0; i < LAGS_WAVE; ++i) acc[i] = fma(av[s], bv[s + i], acc[i]);
         }
     }
     if (!live) return;
     const double n0 = a.a0[j];
-    double *out = a.R + j * a.L + (kb - a.k0) + AC_LAGS_WAVE * wave;
+    double *out = a.R + j * a.L + (kb - a.k0) + LAGS_WAVE * wave;
 #pragma unroll
-    for (int i = 0; i < AC_LAGS_WAVE; ++i) {
-        const long long k = kb + AC_LAGS_WAVE * wave + i;
+    for (int i = 0; i < LAGS_WAVE; ++i) {
+        const long long k = kb + LAGS_WAVE * wave + i;
         // emcee divides acf by acf[0]: lag 0 is 1 exactly (NaN for a constant series)
         if (k < a.n_t) out[i] = k == 0 ? n0 / n0 : acc[i] / n0;
     }
 }
 
-// Walker sums of the round's normalised lags, in groups of AC_WALKERS_GROUP walkers: workgroup (ed, g) adds
-// walkers [g*AC_WALKERS_GROUP, ...) of (e, d) in order, one lane per lag, into part[(ed*G + g)*L + kk].
+// Walker sums of the round's normalised lags, in groups of LAG_GROUP walkers: workgroup (ed, g) adds
+// walkers [g*LAG_GROUP, ...) of (e, d) in order, one lane per lag, into part[(ed*G + g)*L + kk].
 // (A large ensemble spreads its walkers over many workgroups; the window kernel adds the groups in order.)
 __global__ __launch_bounds__(64) void k_ac_walker_sums(const AcArgs a, double *part, long long G)
 {
@@ -161,7 +149,7 @@ __global__ __launch_bounds__(64) void k_ac_walker_sums(const AcArgs a, double *p
     if (a.win[ed] >= 0) return;
     const long long e = ed / a.ndim;
     const int d = (int)(ed % a.ndim);
-    const long long w0 = g * AC_WALKERS_GROUP, w1 = w0 + AC_WALKERS_GROUP < a.Wp ? w0 + AC_WALKERS_GROUP : a.Wp;
+    const long long w0 = g * LAG_GROUP, w1 = w0 + LAG_GROUP < a.Wp ? w0 + LAG_GROUP : a.Wp;
     const double *col = a.R + ((e * a.Wp + w0) * a.ndim + d) * a.L;
     const long long step = (long long)a.ndim * a.L;
     const long long n_round = a.n_t - a.k0 < a.L ? a.n_t - a.k0 : a.L;
@@ -224,20 +212,8 @@ __global__ __launch_bounds__(64) void k_ac_window(const AcArgs a, const double *
     }
 }
 
-// lags per round: enough lag workgroups to fill the chip next to the tiles, no more than the chain has
-long long round_lags(long long n_t, long long M)
-{
-    const long long tiles = (M + AC_TILE - 1) / AC_TILE;
-    long long nb = (AC_TARGET_BLOCKS + tiles - 1) / tiles;
-    const long long need = (n_t + AC_LAG_BLOCK - 1) / AC_LAG_BLOCK;
-    if (nb > need) nb = need;
-    if (nb > 65535) nb = 65535;
-    if (nb < 1) nb = 1;
-    return nb * AC_LAG_BLOCK;
-}
-
 struct Layout {
-    long long M, L;
+    long long M, tiles, L;
     long long G;                       // walker groups
     size_t mean, a0, R, part, cs, win, total;
 };
@@ -246,12 +222,13 @@ Layout layout(long long n_t, long long E, long long Wp, int ndim)
 {
     Layout l{};
     l.M = E * Wp * ndim;
-    l.L = round_lags(n_t, l.M);
+    l.tiles = (l.M + LAG_TILE - 1) / LAG_TILE;
+    l.L = round_lags(n_t, l.tiles);
     const long long P = E * ndim;
     l.mean = 0;
     l.a0 = l.mean + align256((size_t)l.M * 8);
     l.R = l.a0 + align256((size_t)l.M * 8);
-    l.G = (Wp + AC_WALKERS_GROUP - 1) / AC_WALKERS_GROUP;
+    l.G = (Wp + LAG_GROUP - 1) / LAG_GROUP;
     l.part = l.R + align256((size_t)l.M * (size_t)l.L * 8);
     l.cs = l.part + align256((size_t)P * (size_t)l.G * (size_t)l.L * 8);
     l.win = l.cs + align256((size_t)P * 8);
@@ -263,8 +240,8 @@ bool shape_ok(int64_t n_samples, int64_t E, int64_t Wp, int ndim)
 {
     if (n_samples < 1 || E < 1 || Wp < 1 || ndim < 1 || ndim > BISIP_MAX_NDIM) return false;
     if (E > 0x7fffffffLL / ndim) return false;                        // one window workgroup per (e, d)
-    if (Wp > (0x7fffffffLL * AC_TILE) / (E * ndim)) return false;     // tiles within one grid dimension
-    if (Wp > 65535LL * AC_WALKERS_GROUP) return false;                // walker groups within grid dimension y
+    if (Wp > (0x7fffffffLL * LAG_TILE) / (E * ndim)) return false;    // tiles within one grid dimension
+    if (Wp > 65535LL * LAG_GROUP) return false;                       // walker groups within grid dimension y
     return true;
 }
 
@@ -301,16 +278,16 @@ int bisip_chain_autocorr_time_dev(const double *d_chain, int64_t n_samples, int6
     a.win = (long long *)(base + l.win);
     a.tau = d_tau;
     a.window_out = (long long *)d_window;
-    const long long P = n_ensembles * ndim, tiles = (l.M + AC_TILE - 1) / AC_TILE;
+    const long long P = n_ensembles * ndim;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_ac_init, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_ac_prep, dim3((unsigned)tiles), dim3(AC_PREP_WAVES * 64), 0, st, a,
+    hipLaunchKernelGGL(k_ac_prep, dim3((unsigned)l.tiles), dim3(LAG_PREP_WAVES * 64), 0, st, a,
                        (double *)(base + l.mean), (double *)(base + l.a0));
     HIP_TRY(hipGetLastError());
     for (long long k0 = 0; k0 < n_samples; k0 += l.L) {
         a.k0 = k0;
-        const long long nb = (n_samples - k0 < l.L ? n_samples - k0 + AC_LAG_BLOCK - 1 : l.L) / AC_LAG_BLOCK;
-        hipLaunchKernelGGL(k_ac_lags, dim3((unsigned)tiles, (unsigned)nb), dim3(AC_WAVES * 64), 0, st, a);
+        const long long nb = round_blocks(n_samples, k0, l.L);
+        hipLaunchKernelGGL(k_ac_lags, dim3((unsigned)l.tiles, (unsigned)nb), dim3(LAG_WAVES * 64), 0, st, a);
         double *part = (double *)(base + l.part);
         hipLaunchKernelGGL(k_ac_walker_sums, dim3((unsigned)P, (unsigned)l.G), dim3(64), 0, st, a, part, l.G);
         hipLaunchKernelGGL(k_ac_window, dim3((unsigned)P), dim3(64), 0, st, a, (const double *)part, l.G);

@@ -10,9 +10,8 @@
 //   1. k_ess_prep: mean of every series from sums shifted by its first sample (a constant chain has mean exactly its
 //      value and centred samples exactly 0), its min and max (NaN when a value is not finite); one workgroup per tile of
 //      64 series, the samples split over its 16 waves and the partial sums added in a fixed order;
-//   2. k_ess_lags: a round of Lr lags: (tile of 64 series) x (block of 64 lags) as k_ac_lags of chain_autocorr.hip -- the
-//      centred samples of the tile go through LDS, every lane keeps 16 lag accumulators in registers; the pairs (t, t + k)
-//      stay inside the half; writes the raw lag sums of the round into the workspace (Lr per series);
+//   2. k_ess_lags: a round of Lr lags on the lag-sum tile of chain_lags.h; the pairs (t, t + k) stay inside the half;
+//      writes the raw lag sums of the round into the workspace (Lr per series);
 //   3. k_ess_chain_sums: the round's lag sums added over the chains of every pair -- lanes over lags, groups of 256 chains
 //      in order, the scan adds the groups in order;
 //   4. k_ess_scan: one wave per pair.  In round 0 it reduces the chains' means (their variance, two passes), minima and
@@ -23,21 +22,13 @@
 //      marked done; tiles whose pairs are all done leave the later rounds at once.
 // Rounds are enqueued without a host synchronisation.  No floating-point atomics: the same chain gives the same bits
 // every call.
-#include "chain.h"
+#include "chain_lags.h"
 
 using namespace bisip;
 using namespace bisip::host;
 
 namespace {
 
-constexpr int ES_TILE = 64;        // series per tile (one per lane)
-constexpr int ES_LAGS_WAVE = 16;   // lag accumulators per lane
-constexpr int ES_WAVES = 4;        // waves of a lag workgroup
-constexpr int ES_LAG_BLOCK = ES_LAGS_WAVE * ES_WAVES;   // lags per lag workgroup
-constexpr int ES_T = 32;           // samples staged per pass
-constexpr int ES_TARGET_BLOCKS = 512;                   // two lag workgroups per compute unit (64 KiB of LDS each)
-constexpr int ES_PREP_WAVES = 16;
-constexpr int ES_CHAINS_GROUP = 256;                    // chains one k_ess_chain_sums workgroup adds
 constexpr int ES_CHUNK = 256;                           // lags the scan stages in LDS at a time (even)
 constexpr int ESS_MAX_THRESHOLDS = 8;
 constexpr int ES_STATE = 8;        // doubles of scan state per pair
@@ -75,12 +66,12 @@ __global__ __launch_bounds__(256) void k_ess_init(const EssArgs a)
 }
 
 // mean, min and max of 64 series; wave q takes samples q, q + 16, ... of the half.  grid (tiles, nthr * splits)
-__global__ __launch_bounds__(ES_PREP_WAVES * 64) void k_ess_prep(const EssArgs a)
+__global__ __launch_bounds__(LAG_PREP_WAVES * 64) void k_ess_prep(const EssArgs a)
 {
-    __shared__ double ps[ES_PREP_WAVES][ES_TILE], plo[ES_PREP_WAVES][ES_TILE], phi[ES_PREP_WAVES][ES_TILE];
-    __shared__ int pbad[ES_PREP_WAVES][ES_TILE];
+    __shared__ double ps[LAG_PREP_WAVES][LAG_TILE], plo[LAG_PREP_WAVES][LAG_TILE], phi[LAG_PREP_WAVES][LAG_TILE];
+    __shared__ int pbad[LAG_PREP_WAVES][LAG_TILE];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long j = (long long)blockIdx.x * ES_TILE + lane;
+    const long long j = (long long)blockIdx.x * LAG_TILE + lane;
     const long long z = blockIdx.y, v = z / a.splits, half = z - v * a.splits;
     const bool live = j < a.C, ind = a.thr != nullptr;
     double thr = 0.0, c = 0.0, s = 0.0, lo = __builtin_inf(), hi = -__builtin_inf();
@@ -91,7 +82,7 @@ __global__ __launch_bounds__(ES_PREP_WAVES * 64) void k_ess_prep(const EssArgs a
         if (ind) thr = a.thr[(v * a.E + e) * a.ndim + d];
         const double *x = a.chain + (half ? a.start1 : 0) * a.stride + j;
         c = es_value(x[0], ind, thr);
-        for (long long t = wave; t < a.L; t += ES_PREP_WAVES) {
+        for (long long t = wave; t < a.L; t += LAG_PREP_WAVES) {
             const double val = es_value(x[t * a.stride], ind, thr);
             s += val - c;
             lo = fmin(lo, val);
@@ -103,7 +94,7 @@ __global__ __launch_bounds__(ES_PREP_WAVES * 64) void k_ess_prep(const EssArgs a
     __syncthreads();
     if (wave == 0 && live) {
         double tot = 0.0;
-        for (int q = 0; q < ES_PREP_WAVES; ++q) {
+        for (int q = 0; q < LAG_PREP_WAVES; ++q) {
             tot += ps[q][lane];
             lo = fmin(lo, plo[q][lane]);
             hi = fmax(hi, phi[q][lane]);
@@ -117,17 +108,16 @@ __global__ __launch_bounds__(ES_PREP_WAVES * 64) void k_ess_prep(const EssArgs a
 }
 
 // One round's lags [k0, k0 + Lr) of 64 series of one (threshold, half): grid (tiles, lag blocks, nthr * splits).
-// Workgroup (tile, b) owns lags kb = k0 + 64 b ... kb + 63, wave w the 16 lags kb + 16 w + i.  acc_i = sum_t y_t y_{t + kb
-// + 16 w + i} over t < L - kb, with y = 0 beyond the half (a zero product adds nothing).  Per pass the LDS holds y[t0, t0
-// + 32) (A) and y[t0 + kb, t0 + kb + 96) (B) of the tile, one lane's series per column.
-__global__ __launch_bounds__(ES_WAVES * 64) void k_ess_lags(const EssArgs a)
+// Workgroup (tile, b) takes the lag sums of lags kb = k0 + 64 b ... kb + 63 over the L samples of the half on the tile of
+// chain_lags.h (the loop is k_ac_lags' of chain_autocorr.hip) and stores them as they are.
+__global__ __launch_bounds__(LAG_WAVES * 64) void k_ess_lags(const EssArgs a)
 {
-    __shared__ double A[ES_T][ES_TILE];
-    __shared__ double B[ES_T + ES_LAG_BLOCK][ES_TILE];
+    __shared__ double A[LAG_T][LAG_TILE];
+    __shared__ double B[LAG_T + LAG_BLOCK][LAG_TILE];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long kb = a.k0 + (long long)blockIdx.y * ES_LAG_BLOCK;
+    const long long kb = a.k0 + (long long)blockIdx.y * LAG_BLOCK;
     if (kb >= a.L) return;
-    const long long j = (long long)blockIdx.x * ES_TILE + lane;
+    const long long j = (long long)blockIdx.x * LAG_TILE + lane;
     const long long z = blockIdx.z, v = z / a.splits, half = z - v * a.splits;
     const bool live = j < a.C, ind = a.thr != nullptr;
     // the tile leaves when every series in it belongs to a pair whose sequence has ended
@@ -146,36 +136,36 @@ __global__ __launch_bounds__(ES_WAVES * 64) void k_ess_lags(const EssArgs a)
     const double *x = a.chain + (half ? a.start1 : 0) * a.stride + (live ? j : 0);
     auto y = [&](long long t) { return live && t < a.L ? es_value(x[t * a.stride], ind, thr) - m : 0.0; };
 
-    double acc[ES_LAGS_WAVE];
+    double acc[LAGS_WAVE];
 #pragma unroll
-    for (int i = 0; i < ES_LAGS_WAVE; ++i) acc[i] = 0.0;
+    for (int i = 0; i < LAGS_WAVE; ++i) acc[i] = 0.0;
     const long long t_end = a.L - kb;       // samples that still meet a partner at lag kb
-    for (long long t0 = 0; t0 < t_end; t0 += ES_T) {
+    for (long long t0 = 0; t0 < t_end; t0 += LAG_T) {
         __syncthreads();                    // the previous pass has read A and B
-        for (int r = wave; r < ES_T; r += ES_WAVES) A[r][lane] = y(t0 + r);
-        for (int r = wave; r < ES_T + ES_LAG_BLOCK; r += ES_WAVES) B[r][lane] = y(t0 + kb + r);
+        for (int r = wave; r < LAG_T; r += LAG_WAVES) A[r][lane] = y(t0 + r);
+        for (int r = wave; r < LAG_T + LAG_BLOCK; r += LAG_WAVES) B[r][lane] = y(t0 + kb + r);
         __syncthreads();
 #pragma unroll
-        for (int sc = 0; sc < ES_T; sc += ES_LAGS_WAVE) {
-            double av[ES_LAGS_WAVE], bv[2 * ES_LAGS_WAVE];
+        for (int sc = 0; sc < LAG_T; sc += LAGS_WAVE) {
+            double av[LAGS_WAVE], bv[2 * LAGS_WAVE];
 #pragma unroll
-            for (int s = 0; s < ES_LAGS_WAVE; ++s) av[s] = A[sc + s][lane];
+            for (int s = 0; s < LAGS_WAVE; ++s) av[s] = A[sc + s][lane];
 #pragma unroll
-            for (int q = 0; q < 2 * ES_LAGS_WAVE; ++q) bv[q] = B[sc + ES_LAGS_WAVE * wave + q][lane];
+            for (int q = 0; q < 2 * LAGS_WAVE; ++q) bv[q] = B[sc + LAGS_WAVE * wave + q][lane];
 #pragma unroll
-            for (int s = 0; s < ES_LAGS_WAVE; ++s)
+            for (int s = 0; s < LAGS_WAVE; ++s)
 #pragma unroll
-                for (int i = 0; i < ES_LAGS_WAVE; ++i) acc[i] = fma(av[s], bv[s + i], acc[i]);
+                for (int i = 0; i < LAGS_WAVE; ++i) acc[i] = fma(av[s], bv[s + i], acc[i]);
         }
     }
     if (!live) return;
-    double *out = a.R + (z * a.C + j) * a.Lr + (kb - a.k0) + ES_LAGS_WAVE * wave;
+    double *out = a.R + (z * a.C + j) * a.Lr + (kb - a.k0) + LAGS_WAVE * wave;
 #pragma unroll
-    for (int i = 0; i < ES_LAGS_WAVE; ++i)
-        if (kb + ES_LAGS_WAVE * wave + i < a.L) out[i] = acc[i];
+    for (int i = 0; i < LAGS_WAVE; ++i)
+        if (kb + LAGS_WAVE * wave + i < a.L) out[i] = acc[i];
 }
 
-// Chain sums of the round's lags, in groups of ES_CHAINS_GROUP chains: workgroup (p, g) adds chains [g * 256, ...) of
+// Chain sums of the round's lags, in groups of LAG_GROUP chains: workgroup (p, g) adds chains [g * 256, ...) of
 // pair p in order, one lane per lag, into part[(p * G + g) * Lr + kk].
 __global__ __launch_bounds__(64) void k_ess_chain_sums(const EssArgs a)
 {
@@ -184,20 +174,13 @@ __global__ __launch_bounds__(64) void k_ess_chain_sums(const EssArgs a)
     const long long per = a.E * a.ndim, v = p / per, ed = p - v * per, e = ed / a.ndim;
     const int d = (int)(ed % a.ndim);
     const long long M = a.splits * a.Wp;
-    const long long c0 = g * ES_CHAINS_GROUP, c1 = c0 + ES_CHAINS_GROUP < M ? c0 + ES_CHAINS_GROUP : M;
+    const long long c0 = g * LAG_GROUP, c1 = c0 + LAG_GROUP < M ? c0 + LAG_GROUP : M;
     const long long n_round = a.L - a.k0 < a.Lr ? a.L - a.k0 : a.Lr;
     for (long long kk = threadIdx.x; kk < n_round; kk += 64) {
         double s = 0.0;
         for (long long c = c0; c < c1; ++c) s += a.R[es_series(a, v, e, d, c) * a.Lr + kk];
         a.part[(p * a.G + g) * a.Lr + kk] = s;
     }
-}
-
-__device__ __forceinline__ double es_wave_sum(double x)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) x += __shfl_xor(x, s, 64);
-    return x;
 }
 
 // One wave per pair: abar_k of the round's lags (lane = lag, the chain groups added in order) staged in LDS, then lane 0
@@ -228,7 +211,7 @@ __global__ __launch_bounds__(64) void k_ess_scan(const EssArgs a)
             lo = fmin(lo, cl);
             hi = fmax(hi, ch);
         }
-        sum = es_wave_sum(sum);
+        sum = wave_sum(sum);
 #pragma unroll
         for (int s = 32; s >= 1; s >>= 1) {
             lo = fmin(lo, __shfl_xor(lo, s, 64));
@@ -242,7 +225,7 @@ __global__ __launch_bounds__(64) void k_ess_scan(const EssArgs a)
             const double dm = a.mean[es_series(a, v, e, d, c)] - mm;
             t2 = fma(dm, dm, t2);
         }
-        t2 = es_wave_sum(t2);
+        t2 = wave_sum(t2);
         if (M > 1) var_means = t2 / (double)(M - 1);
         // (every lane holds the same bad, lo and hi: the exits are uniform)
         if (bad || hi - lo < 1e-15) {
@@ -315,17 +298,6 @@ __global__ __launch_bounds__(64) void k_ess_scan(const EssArgs a)
     }
 }
 
-// lags per round: enough lag workgroups to fill the chip next to the tiles, no more than a half has
-long long round_lags(long long L, long long tiles_total)
-{
-    long long nb = (ES_TARGET_BLOCKS + tiles_total - 1) / tiles_total;
-    const long long need = (L + ES_LAG_BLOCK - 1) / ES_LAG_BLOCK;
-    if (nb > need) nb = need;
-    if (nb > 65535) nb = 65535;
-    if (nb < 1) nb = 1;
-    return nb * ES_LAG_BLOCK;
-}
-
 struct Layout {
     long long L, C, Z, P, M, G, Lr, tiles;
     size_t mean, cmin, cmax, R, part, state, t, done, total;
@@ -337,8 +309,8 @@ bool ess_shape_ok(int64_t n, int64_t E, int64_t Wp, int ndim, int splits, int n_
     if (n_threshold < 0 || n_threshold > ESS_MAX_THRESHOLDS) return false;
     if (n < 2 * splits || E < 1 || Wp < 1) return false;
     if (n > 0x7fffffffLL || E > 0x7fffffffLL / (ndim * ESS_MAX_THRESHOLDS)) return false;   // one scan workgroup per pair
-    if (Wp > (0x7fffffffLL * ES_TILE) / (E * ndim)) return false;                           // tiles within grid dimension x
-    if (2 * Wp > 65535LL * ES_CHAINS_GROUP) return false;                                   // chain groups within dimension y
+    if (Wp > (0x7fffffffLL * LAG_TILE) / (E * ndim)) return false;                          // tiles within grid dimension x
+    if (2 * Wp > 65535LL * LAG_GROUP) return false;                                         // chain groups within dimension y
     return true;
 }
 
@@ -351,8 +323,8 @@ Layout ess_layout(long long n, long long E, long long Wp, int ndim, int splits, 
     l.Z = nthr * splits;
     l.P = nthr * E * ndim;
     l.M = splits * Wp;
-    l.G = (l.M + ES_CHAINS_GROUP - 1) / ES_CHAINS_GROUP;
-    l.tiles = (l.C + ES_TILE - 1) / ES_TILE;
+    l.G = (l.M + LAG_GROUP - 1) / LAG_GROUP;
+    l.tiles = (l.C + LAG_TILE - 1) / LAG_TILE;
     l.Lr = round_lags(l.L, l.tiles * l.Z);
     const size_t series = align256((size_t)l.Z * (size_t)l.C * 8);
     l.mean = 0;
@@ -518,12 +490,12 @@ int bisip_chain_ess_dev(const double *d_chain, int64_t n_samples, int64_t sample
     a.ess = d_ess;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_ess_init, dim3((unsigned)((l.P + 255) / 256)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_ess_prep, dim3((unsigned)l.tiles, (unsigned)l.Z), dim3(ES_PREP_WAVES * 64), 0, st, a);
+    hipLaunchKernelGGL(k_ess_prep, dim3((unsigned)l.tiles, (unsigned)l.Z), dim3(LAG_PREP_WAVES * 64), 0, st, a);
     HIP_TRY(hipGetLastError());
     for (long long k0 = 0; k0 < l.L; k0 += l.Lr) {
         a.k0 = k0;
-        const long long nb = (l.L - k0 < l.Lr ? l.L - k0 + ES_LAG_BLOCK - 1 : l.Lr) / ES_LAG_BLOCK;
-        hipLaunchKernelGGL(k_ess_lags, dim3((unsigned)l.tiles, (unsigned)nb, (unsigned)l.Z), dim3(ES_WAVES * 64), 0, st, a);
+        const long long nb = round_blocks(l.L, k0, l.Lr);
+        hipLaunchKernelGGL(k_ess_lags, dim3((unsigned)l.tiles, (unsigned)nb, (unsigned)l.Z), dim3(LAG_WAVES * 64), 0, st, a);
         hipLaunchKernelGGL(k_ess_chain_sums, dim3((unsigned)l.P, (unsigned)l.G), dim3(64), 0, st, a);
         hipLaunchKernelGGL(k_ess_scan, dim3((unsigned)l.P), dim3(64), 0, st, a);
         HIP_TRY(hipGetLastError());

@@ -63,15 +63,13 @@ struct TraceArgs {
 };
 
 // The sum of a column of n values as one wave takes it, the order both paths keep: lane l adds values l, l + 64, ... in
-// turn onto 0.0, then lanes d = 32, 16, ..., 1 apart are added pairwise.  f(w) = value w.
+// turn onto 0.0, then lanes 32, 16, ..., 1 apart are added pairwise (wave_sum).  f(w) = value w.
 template <typename F>
 __device__ __forceinline__ double trace_column_sum(int lane, long long n, F &&f)
 {
     double acc = 0.0;
     for (long long w = lane; w < n; w += 64) acc += f(w);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    return acc;
+    return wave_sum(acc);
 }
 
 __device__ __forceinline__ void tr_ce(unsigned long long &x, unsigned long long &y, bool asc)

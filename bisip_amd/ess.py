@@ -257,9 +257,9 @@ def mcse_mean(x, split=True):
 
 # -- on the device -------------------------------------------------------------------------------------------------------
 def round_lags(n, n_ensembles, walkers_per_ensemble, ndim, split=True, n_threshold=0):
-    """How many lags bisip_chain_ess_dev takes per round (include/bisip_hip.h) -- a function of the shape alone: 64 *
-    min(ceil(L / 64), max(1, ceil(512 / (tiles * series)))) with ``tiles = ceil(columns / 64)`` and ``series = max(1,
-    n_threshold) * splits``."""
+    """How many lags bisip_chain_ess_dev takes per round -- a function of the shape alone: round_lags of
+    bisip_amd/csrc/chain_lags.h (whose tile constants the numbers below restate) on the ``L`` samples of a half and the
+    ``ceil(columns / 64) * max(1, n_threshold) * splits`` tiles of every series set."""
     splits = 2 if split else 1
     L = int(n) // splits
     tiles = -(-(int(n_ensembles) * int(walkers_per_ensemble) * int(ndim)) // 64) * max(1, int(n_threshold)) * splits
