@@ -8,7 +8,8 @@
 //      (ensemble, parameter), coalesced on both sides;
 //   2. the two order statistics each percentile needs: radix selection, one workgroup per column
 //      (k_segmented_select) -- or, for more than 8 percentiles of many columns, a rocPRIM segmented
-//      radix sort of the E*ndim columns (library sort: hipCUB header) followed by
+//      radix sort of the E*ndim columns (library sort: hipCUB header), k_order_zeros (-0.0 before 0.0, as the
+//      selection has them) and
 //   3. k_percentile_lerp: NumPy's 'linear' rule between the two neighbouring order statistics
 //      (indices and weights are computed on the host exactly as numpy does).
 //
@@ -76,6 +77,36 @@ __global__ __launch_bounds__(256) void k_gather_columns_tiled(const GatherArgs a
         const int q = idx / nr, r = idx - q * nr;
         dst[(long long)q * n + r] = tile[r][q];
     }
+}
+
+// rocPRIM's radix sort takes -0.0 and 0.0 for one key and leaves them in the order they came; the selection's keys put
+// -0.0 first.  One workgroup per sorted column gives its run of zeros that order, so that the order statistics of the sort
+// path -- and with them the sign of a percentile that is zero -- are the selection's, whatever order the zeros came in.
+__global__ __launch_bounds__(256) void k_order_zeros(double *sorted, long long n)
+{
+    __shared__ long long z[2];          // [z[0], z[1]): the zeros of the column
+    __shared__ unsigned negative;
+    double *__restrict__ c = sorted + (long long)blockIdx.x * n;
+    if (threadIdx.x < 2) {              // the first key >= that of -0.0 | > that of 0.0 (NaNs lie beyond the ends in keys, too)
+        const unsigned long long bound = threadIdx.x == 0 ? select_key(-0.0) : select_key(0.0) + 1ull;
+        long long lo = 0, hi = n;
+        while (lo < hi) {
+            const long long mid = lo + (hi - lo) / 2;
+            if (select_key(c[mid]) < bound) lo = mid + 1; else hi = mid;
+        }
+        z[threadIdx.x] = lo;
+    }
+    if (threadIdx.x == 0) negative = 0;
+    __syncthreads();
+    const long long z0 = z[0], zeros = z[1] - z0;
+    if (zeros < 2) return;              // the same in every lane
+    unsigned mine = 0;
+    for (long long i = threadIdx.x; i < zeros; i += 256) mine += select_key(c[z0 + i]) == select_key(-0.0);
+    if (mine) atomicAdd(&negative, mine);
+    __syncthreads();
+    const long long m = negative;
+    if (m == 0 || m == zeros) return;
+    for (long long i = threadIdx.x; i < zeros; i += 256) c[z0 + i] = i < m ? -0.0 : 0.0;
 }
 
 struct LerpArgs {
@@ -493,6 +524,8 @@ static int percentiles_impl(const double *d_chain, int64_t n_samples, int64_t sa
 
     rc = sort_segments(d_temp, temp, cols, sorted, items, columns, n, st);
     if (rc != BISIP_OK) return rc;
+    hipLaunchKernelGGL(k_order_zeros, dim3((unsigned)columns), dim3(256), 0, st, sorted, (long long)n);
+    HIP_TRY(hipGetLastError());
     LerpArgs l{sorted, n, columns, n_percentiles, d_lo, d_t, d_out};
     hipLaunchKernelGGL(k_percentile_lerp, dim3((unsigned)((columns * n_percentiles + 255) / 256)), dim3(256), 0, st, l);
     HIP_TRY(hipGetLastError());
