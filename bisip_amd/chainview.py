@@ -5,11 +5,12 @@ device tensor and carries the stream and allocator the summary works with.  ``_D
 keeps the stored samples of a run there (bisip_amd.sampler writes them, bisip_amd.summaries views them).
 ``device_moments`` and ``device_percentiles`` are the two summaries that any view has (bisip_chain_moments_dev,
 bisip_chain_percentiles_dev); the others are in bisip_amd.autocorr, bisip_amd.histogram and bisip_amd.decomposition.
+``moment_splits`` and ``ordered_moments`` are the summation order of bisip_chain_moments_dev in NumPy, bit for bit.
 """
 
 import numpy as np
 
-__all__ = ('used_range', 'ChainView', 'device_moments', 'device_percentiles')
+__all__ = ('used_range', 'ChainView', 'device_moments', 'device_percentiles', 'moment_splits', 'ordered_moments')
 
 
 def used_range(n_total, discard, thin):
@@ -145,6 +146,105 @@ def device_moments(view):
                            view.stream)
     view.synchronize()
     return mean.cpu().numpy(), std.cpu().numpy()
+
+
+# -- the device's order of summation ------------------------------------------------------------------------------------
+MOMENT_WORKGROUPS, MOMENT_SPLIT_MIN, MOMENT_THREADS = 4096, 4, 256      # chain_moments.hip: moment_splits, the block
+
+
+def moment_splits(n_samples, n_ensembles):
+    """Into how many ranges of samples bisip_chain_moments_dev cuts a chain: ``max(1, min(ceil(4096 / E), n / 4))`` -- a
+    function of the shape alone.  Split ``sp`` takes samples ``[n * sp // splits, n * (sp + 1) // splits)``; its workspace
+    is ``E * splits * ndim`` doubles."""
+    n, E = int(n_samples), int(n_ensembles)
+    return max(1, min(-(-MOMENT_WORKGROUPS // E), n // MOMENT_SPLIT_MIN))
+
+
+def exact_fma(a, b, c):
+    """``a * b + c`` of three doubles with one rounding (IEEE fusedMultiplyAdd, round to nearest even), in rational
+    arithmetic: Python 3.10 has no math.fma."""
+    import math
+    from fractions import Fraction
+    a, b, c = float(a), float(b), float(c)
+    if not (math.isfinite(a) and math.isfinite(b)):
+        with np.errstate(all='ignore'):
+            return float(np.float64(a) * np.float64(b) + np.float64(c))       # (the product is inf or NaN exactly)
+    if not math.isfinite(c):
+        return c                                                             # (a finite product, however large)
+    exact = Fraction(a) * Fraction(b) + Fraction(c)
+    if exact == 0:
+        if a * b == 0.0:                 # (a zero product is exact: the sum of two zeros has IEEE's sign)
+            return a * b + c
+        return 0.0                       # x + (-x): +0 when rounding to nearest
+    try:
+        r = float(exact)                 # (int / int is correctly rounded, subnormals included)
+    except OverflowError:
+        return math.inf if exact > 0 else -math.inf
+    return -0.0 if r == 0.0 and exact < 0 else r
+
+
+def ordered_moments(x, n_ensembles=1):
+    """``(mean, std)``, ``(n_ensembles, ndim)`` each, of a chain ``(n, n_ensembles * Wp, ndim)`` with the bits
+    bisip_chain_moments_dev produces, in the order include/bisip_hip.h states: samples in ``moment_splits`` ranges; lane
+    ``t`` of ``(256 // ndim) * ndim`` owns the doubles ``t, t + lanes, ...`` of the ensemble's ``Wp * ndim`` of a sample;
+    four accumulators per lane over groups of four samples, the left-over samples to the first, ``(a0 + a1) + (a2 + a3)``;
+    lanes of a parameter, then splits, in ascending order.  The second pass is ``fma(d, d, acc)`` with ``d = x - mean``,
+    taken exactly value by value in Python (``exact_fma``): some 10 us per value, so this is for chains of a few ten
+    thousand values -- the small shapes of the tests -- and not for a fit's."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim != 3:
+        raise ValueError('the chain must be (n, walkers, ndim)')
+    n, W, ndim = x.shape
+    E = int(n_ensembles)
+    if n < 1 or W < 1 or ndim < 1 or E < 1 or W % E:
+        raise ValueError(f'a chain {x.shape} does not divide into {E} ensembles')
+    Wp = W // E
+    length = Wp * ndim                                   # doubles of an ensemble per sample
+    lanes = (MOMENT_THREADS // ndim) * ndim
+    if lanes < 1:
+        raise ValueError(f'ndim={ndim} out of range')
+    splits = moment_splits(n, E)
+    v = x.reshape(n, E, length)
+    fma = np.frompyfunc(exact_fma, 3, 1)
+
+    # the doubles i ... i + k - 1 of a sample go to lanes 0 ... k - 1 (a lane beyond the last double adds nothing)
+    turns = [(i, min(lanes, length - i)) for i in range(0, length, lanes)]
+
+    def sweep(mean):
+        m = None if mean is None else np.tile(mean, (1, lanes // ndim))     # lane t: parameter t % ndim
+
+        def add(acc, s, i, k):
+            if m is None:
+                acc[:, :k] = acc[:, :k] + v[s, :, i:i + k]
+            else:
+                d = v[s, :, i:i + k] - m[:, :k]
+                acc[:, :k] = fma(d, d, acc[:, :k]).astype(np.float64)
+
+        total = np.zeros((E, ndim))
+        for sp in range(splits):
+            s, s1 = n * sp // splits, n * (sp + 1) // splits
+            acc = np.zeros((4, E, lanes))
+            while s + 4 <= s1:
+                for i, k in turns:                       # for each double of the lane in turn, sample s + j to j
+                    for j in range(4):
+                        add(acc[j], s + j, i, k)
+                s += 4
+            while s < s1:
+                for i, k in turns:
+                    add(acc[0], s, i, k)
+                s += 1
+            lane = (acc[0] + acc[1]) + (acc[2] + acc[3])
+            part = np.zeros((E, ndim))
+            for k in range(lanes // ndim):
+                part = part + lane[:, k * ndim:(k + 1) * ndim]
+            total = total + part
+        return total
+
+    with np.errstate(all='ignore'):
+        count = float(n) * float(Wp)
+        mean = sweep(None) / count
+        std = np.sqrt(sweep(mean) / count)
+    return mean, std
 
 
 def device_percentiles(view, p):

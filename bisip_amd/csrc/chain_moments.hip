@@ -11,6 +11,16 @@
 // parameter t % ndim and keeps ONE running sum -- no dynamic register indexing, coalesced
 // loads.  Partial sums are combined in a fixed order (lanes, then splits): the result does
 // not depend on scheduling.  Pass 0: mean.  Pass 1: sum (x - mean)^2 -> population std.
+//
+// The order, as include/bisip_hip.h states it and bisip_amd.chainview.ordered_moments reproduces it bit for bit:
+//   splits = max(1, min(ceil(4096 / E), n / 4)); split sp takes samples [n * sp / splits, n * (sp + 1) / splits).
+//   lanes = (256 / ndim) * ndim; lane t owns the doubles t, t + lanes, ... of the ensemble's Wp * ndim of a sample.
+//   Four accumulators per lane from 0.0: samples in groups of four from the start of the split, for each of the lane's
+//   doubles in turn sample s + j to accumulator j; the one to three samples left over to accumulator 0; the lane's sum is
+//   (a0 + a1) + (a2 + a3).  Lanes q, q + ndim, ... in ascending order onto 0.0; splits in ascending order onto 0.0.
+//   Pass 0 adds x; mean = sum / (double(n) * double(Wp)).  Pass 1: d = x - mean, acc = fma(d, d, acc); std = sqrt(sum /
+//   count).  The workspace is counted in DOUBLES (E * splits * ndim), unlike every later *_workspace.
+// Any change here changes bits that tests/test_gpu_moments.py holds: change the header and ordered_moments with it.
 #include "chain.h"
 
 using namespace bisip;

@@ -317,8 +317,26 @@ int bisip_stretch_persistent_dev(bisip_ctx *ctx, const bisip_persist_args *args,
  * d_chain points at the first sample to use; sample k is at d_chain + k*sample_stride
  * doubles and holds (n_ensembles*walkers_per_ensemble, ndim) rows, ensemble e owning rows
  * [e*Wp, (e+1)*Wp).  (discard/thin of get_chain: offset the pointer, multiply the stride.)
- * d_mean, d_std: (n_ensembles, ndim).  d_work: bisip_chain_moments_workspace() doubles.
- * Two passes (mean, then centred squares), fixed summation order, asynchronous on stream. */
+ * d_mean, d_std: (n_ensembles, ndim); ndim 1 ... BISIP_MAX_NDIM, n_ensembles < 2^31.
+ * Two passes over the chain (mean, then centred squares), each in this order; E = n_ensembles, Wp =
+ * walkers_per_ensemble, n = n_samples, integer divisions round down:
+ *   splits = max(1, min(ceil(4096 / E), n / 4)); split sp takes samples [n * sp / splits, n * (sp + 1) / splits).
+ *   Lanes: of 256, the first lanes = (256 / ndim) * ndim work.  Lane t owns the doubles t, t + lanes, t + 2 lanes, ...
+ *     of the Wp * ndim doubles that the ensemble has in a sample; every one of them is parameter t % ndim.
+ *   Accumulators: four per lane, each from 0.0.  The samples of the split go in groups of four from its start: within a
+ *     group, for each of the lane's doubles in turn, sample s + j goes to accumulator j (j = 0, 1, 2, 3 in this order).
+ *     The one to three samples left over go to accumulator 0, sample after sample, the lane's doubles in turn.  The
+ *     lane's sum is (a0 + a1) + (a2 + a3).
+ *   Per parameter q of a split: the sums of lanes q, q + ndim, q + 2 ndim, ... (< lanes) are added in ascending order
+ *     onto 0.0.  Per (ensemble, parameter): the splits' sums are added in ascending order onto 0.0.
+ *   Pass 0: an accumulator adds x.  mean = sum / count, count = double(n) * double(Wp).
+ *   Pass 1: d = x - mean (one rounding), the accumulator becomes fma(d, d, acc) (one rounding).  std = sqrt(sum / count).
+ * IEEE throughout: a NaN in an (ensemble, parameter) makes its mean and std NaN; +inf or -inf alone that mean and a NaN
+ * std; both, two NaN; nothing else changes.  Squares that leave binary64's range give std = +inf or 0.
+ * d_work: bisip_chain_moments_workspace() DOUBLES, not bytes (every later *_workspace counts bytes): E * splits * ndim,
+ * 0 when n_samples, n_ensembles or ndim is below 1.  BISIP_EINVAL and nothing written for a null pointer, a shape out of
+ * range or sample_stride < E * Wp * ndim.  The plan depends on the shape alone, never on the device.  No atomics: the same
+ * bits on every call (chainview.ordered_moments gives them in NumPy).  64-bit offsets.  Asynchronous on stream. */
 int64_t bisip_chain_moments_workspace(int64_t n_samples, int64_t n_ensembles, int ndim);
 int bisip_chain_moments_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride,
                             int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim,

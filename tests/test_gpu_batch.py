@@ -322,6 +322,16 @@ def _close(a, b, tol=MOMENT_TOL):
     assert np.all(np.abs(a - b) <= tol * np.maximum(1.0, np.abs(b))), np.max(np.abs(a - b))
 
 
+def _within_moments_bound(chain, mean, std, c=6):
+    """MOMENT_TOL is absolute below 1; beside it, the first-order bound that tests/moments_bounds.py derives, from the
+    long-double reference of chain (n, E, Wp, ndim).  c = 7: NumPy's std, whose product rounds on its own."""
+    from moments_bounds import assert_within_bounds, reference_and_bounds
+    n, E, Wp, ndim = chain.shape
+    ref = reference_and_bounds(chain.reshape(n, E * Wp, ndim), E, c)
+    assert ref['checked'].all()
+    assert_within_bounds(mean, std, ref)
+
+
 def test_device_chain_is_the_host_chain_and_moments_match_numpy():
     import bisip_amd
     E, Wp = 6, 32
@@ -340,6 +350,11 @@ def test_device_chain_is_the_host_chain_and_moments_match_numpy():
         _close(dev.get_param_mean(discard=discard, thin=thin), flat.mean(axis=1))
         _close(dev.get_param_std(discard=discard, thin=thin), flat.std(axis=1))
         _close(host.get_param_mean(discard=discard, thin=thin), flat.mean(axis=1))
+        chain = host.get_chain(discard=discard, thin=thin)                     # (n, E, Wp, ndim)
+        _within_moments_bound(chain, dev.get_param_mean(discard=discard, thin=thin),
+                              dev.get_param_std(discard=discard, thin=thin))
+        _within_moments_bound(chain, host.get_param_mean(discard=discard, thin=thin),
+                              host.get_param_std(discard=discard, thin=thin), c=7)
     with pytest.raises(ValueError):
         dev.get_param_mean(discard=40)
     assert np.array_equal(dev.get_chain(), host.get_chain())                   # same chain, bit for bit
@@ -371,6 +386,7 @@ def test_chain_moments_entry_point(n, E, Wp, ndim, thin):
     used = full[first::thin].reshape(n, E, Wp, ndim).transpose(1, 0, 2, 3).reshape(E, n * Wp, ndim)
     _close(mean.cpu().numpy(), used.mean(axis=1))
     _close(std.cpu().numpy(), used.std(axis=1))
+    _within_moments_bound(full[first::thin].reshape(n, E, Wp, ndim), mean.cpu().numpy(), std.cpu().numpy())
     with pytest.raises(ValueError):
         _hip.chain_moments_dev(t.data_ptr(), n, 1, E, Wp, ndim, mean.data_ptr(), std.data_ptr(),
                                work.data_ptr(), 0)

@@ -2,7 +2,8 @@
 bisip_rtd_columns_dev) against the long-double yardstick, from the C entry points up to the model and
 SpectraBatch methods.  Bounds: tests/test_decomposition.py.  Summaries add the tolerance the existing
 device-summary tests hold the same kernels to: MOMENT_TOL relative to max(1, |value|) for the mean
-(tests/test_gpu_batch.py), rtol 1e-9 for the std (tests/test_gpu_parity.py); a percentile is 1-Lipschitz in
+(tests/test_gpu_batch.py), rtol 1e-9 for the std (tests/test_gpu_parity.py) -- loose figures kept as they were; what
+the moments kernel itself is held to is the derived bound of tests/moments_bounds.py; a percentile is 1-Lipschitz in
 the max-norm of its column, so it may move by the largest bound of the column plus 4u of its value."""
 
 import warnings

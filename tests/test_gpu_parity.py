@@ -463,6 +463,11 @@ def test_fit_with_the_chain_kept_on_the_device():
     assert np.array_equal(flat, host.get_chain(discard=40, thin=2, flat=True))
     assert np.allclose(mean, flat.mean(axis=0), rtol=1e-12, atol=1e-14)
     assert np.allclose(std, flat.std(axis=0), rtol=1e-9, atol=1e-14)
+    # beside the two tolerances: the first-order bound of the two passes (tests/moments_bounds.py), per parameter
+    from moments_bounds import assert_within_bounds, reference_and_bounds
+    ref = reference_and_bounds(dev.get_chain(discard=40, thin=2), 1)
+    assert ref['checked'].all()
+    assert_within_bounds(mean[None], std[None], ref)
     assert np.allclose(pct, np.percentile(flat, [2.5, 50, 97.5], axis=0), rtol=1e-13, atol=1e-15)
     assert med.shape == (4,) and np.allclose(med, np.percentile(dev.get_chain(discard=40, flat=True), 50, axis=0), rtol=1e-13)
     # model-space percentiles: forward + column sort where the chain lies == the same kernels fed from the host
@@ -478,6 +483,9 @@ def test_fit_with_the_chain_kept_on_the_device():
     dev.sampler.run_mcmc(None, 30)
     assert dev.get_chain().shape == (150, 300, 4) and np.array_equal(dev.get_chain()[:120], host.get_chain())
     assert np.allclose(dev.get_param_std(discard=100), dev.get_chain(discard=100, flat=True).std(axis=0), rtol=1e-9)
+    ref = reference_and_bounds(dev.get_chain(discard=100), 1)
+    assert ref['checked'].all()
+    assert_within_bounds(dev.get_param_mean(discard=100)[None], dev.get_param_std(discard=100)[None], ref)
     # the stored samples nearest to logp = 0 (what fit() measures a reduced kernel on) are found where the
     # chain lies, the same rows as from the host copy
     r_dev, l_dev = dev.sampler.rows_nearest_zero_logp(64)
