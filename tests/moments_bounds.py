@@ -38,6 +38,7 @@ import functools
 
 import numpy as np
 
+import chain_harness
 from convergence_bounds import LD, U, hand_built_chain
 
 # (n, E, Wp, ndim) of bisip_chain_moments_dev.  splits = max(1, min(ceil(4096 / E), n / 4)); lanes = (256 / ndim) * ndim.
@@ -110,11 +111,10 @@ def assert_within_bounds(mean, std, ref, label=''):
 
 
 def assert_same_bits(got, want, what=''):
-    fin = np.isfinite(want)
-    np.testing.assert_array_equal(np.isfinite(got), fin, err_msg=what)
+    """chain_harness.assert_same_bits, and NaN only where ``want`` has NaN, every infinity with its sign."""
+    chain_harness.assert_same_bits(got, want, what)
     np.testing.assert_array_equal(np.isnan(got), np.isnan(want), err_msg=what)
-    np.testing.assert_array_equal(got[fin].view(np.uint64), want[fin].view(np.uint64), err_msg=what)
-    np.testing.assert_array_equal(got[~fin & ~np.isnan(want)], want[~fin & ~np.isnan(want)], err_msg=what)      # +inf / -inf
+    np.testing.assert_array_equal(got[np.isinf(want)], want[np.isinf(want)], err_msg=what)
 
 
 def assert_agrees_with_numpy(mean, std, ref, ref_numpy, np_mean, np_std, label=''):

@@ -9,6 +9,7 @@ import pytest
 
 from bisip_amd import convergence as cv
 from convergence_bounds import LD, assert_within_bounds, hand_built_chain, reference_and_bounds
+from fitted import fitted_on_host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -174,22 +175,6 @@ def test_segment_plan():
 
 
 # -- plumbing -------------------------------------------------------------------------------------------------------
-def gaussian_logp(theta):
-    return -0.5 * np.sum((theta - np.array([1.0, 0.01, 0.0, 0.0])) ** 2 / 1e-4, axis=1)
-
-
-def fitted_on_host():
-    import bisip_amd
-    from bisip_amd.sampler import EnsembleSampler
-    m = bisip_amd.PolynomialDecomposition(bisip_amd.DataFiles()['SIP-K389175'], poly_deg=2, nwalkers=8)
-    np.random.seed(1)
-    s = EnsembleSampler(8, 4, gaussian_logp)
-    s.run_mcmc(np.array([1.0, 0.01, 0.0, 0.0]) + 1e-3 * np.random.randn(8, 4), 20)
-    m._sampler = s
-    m._Inversion__fitted = True
-    return m
-
-
 @pytest.mark.parametrize('kw', [dict(), dict(discard=5, thin=3)])
 def test_inversion_methods_with_the_host_sampler(kw):
     m = fitted_on_host()

@@ -10,6 +10,7 @@ import pytest
 from bisip_amd import covariance as cv
 from convergence_bounds import hand_built_chain
 from covariance_bounds import assert_within, reference_and_bounds, rows_of
+from fitted import fitted_on_host, gaussian_logp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -211,22 +212,6 @@ def test_entry_points_check_their_arguments():
         best(n=0)
     with pytest.raises(ValueError, match='workspace'):
         best(n=1000, work=0)                                 # 8000 rows: two segments
-
-
-def gaussian_logp(theta):
-    return -0.5 * np.sum((theta - np.array([1.0, 0.01, 0.0, 0.0])) ** 2 / 1e-4, axis=1)
-
-
-def fitted_on_host():
-    import bisip_amd
-    from bisip_amd.sampler import EnsembleSampler
-    m = bisip_amd.PolynomialDecomposition(bisip_amd.DataFiles()['SIP-K389175'], poly_deg=2, nwalkers=8)
-    np.random.seed(1)
-    s = EnsembleSampler(8, 4, gaussian_logp)
-    s.run_mcmc(np.array([1.0, 0.01, 0.0, 0.0]) + 1e-3 * np.random.randn(8, 4), 20)
-    m._sampler = s
-    m._Inversion__fitted = True
-    return m
 
 
 @pytest.mark.parametrize('kw', [dict(), dict(discard=5, thin=3)])

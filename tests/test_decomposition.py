@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from bisip_amd.decomposition import INTEGRATING_NAMES, integrating_params, power_sums, rtd
+from fitted import fitted_on_host
 from test_gpu_known_answers import DEBYE_TUTORIAL
 
 U = 2.0 ** -53
@@ -168,24 +169,6 @@ def test_abi_version_and_symbols(hip_lib):
     assert hip_lib.bisip_abi_version() == 6
     for name in ('bisip_rtd_integrals_dev', 'bisip_rtd_columns_dev'):
         assert hasattr(hip_lib, name)
-
-
-def gaussian_logp(theta):
-    return -0.5 * np.sum((theta - np.array([1.0, 0.01, 0.0, 0.0])) ** 2 / 1e-4, axis=1)
-
-
-def fitted_on_host():
-    """A PolynomialDecomposition whose chain comes from the host sampler around a NumPy log-probability: the
-    argument checks run before any device work."""
-    import bisip_amd
-    from bisip_amd.sampler import EnsembleSampler
-    m = bisip_amd.PolynomialDecomposition(bisip_amd.DataFiles()['SIP-K389175'], poly_deg=2, nwalkers=8)
-    np.random.seed(1)
-    s = EnsembleSampler(8, 4, gaussian_logp)
-    s.run_mcmc(np.array([1.0, 0.01, 0.0, 0.0]) + 1e-3 * np.random.randn(8, 4), 20)
-    m._sampler = s
-    m._Inversion__fitted = True
-    return m
 
 
 @pytest.mark.parametrize('method', ['get_integrating_chain', 'get_integrating_mean', 'get_integrating_std',

@@ -10,6 +10,7 @@ import pytest
 import ess_cases as ec
 from bisip_amd import ess as es
 from bisip_amd.autocorr import _acf
+from fitted import fitted_on_host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -298,22 +299,9 @@ def test_entry_points_check_their_arguments():
         rank(nbytes=_hip.chain_rank_normalize_workspace(8, 1, 8, 3) - 1)
 
 
-def fitted_on_host():
-    import bisip_amd
-    from bisip_amd.sampler import EnsembleSampler
-    centre = np.array([1.0, 0.01, 0.0, 0.0])
-    m = bisip_amd.PolynomialDecomposition(bisip_amd.DataFiles()['SIP-K389175'], poly_deg=2, nwalkers=8)
-    np.random.seed(1)
-    s = EnsembleSampler(8, 4, lambda theta: -0.5 * np.sum((theta - centre) ** 2 / 1e-4, axis=1))
-    s.run_mcmc(centre + 1e-3 * np.random.randn(8, 4), 60)
-    m._sampler = s
-    m._Inversion__fitted = True
-    return m
-
-
 @pytest.mark.parametrize('kw', [dict(), dict(discard=11, thin=3)])
 def test_inversion_methods_with_the_host_sampler(kw):
-    m = fitted_on_host()
+    m = fitted_on_host(60)
     chain, lp = m.get_chain(**kw), m._sampler.get_log_prob(**kw)
     for kind in es.KINDS:
         for split in (True, False):
@@ -332,7 +320,7 @@ def test_inversion_methods_with_the_host_sampler(kw):
 
 @pytest.mark.parametrize('method', ['get_ess', 'get_mcse_mean', 'get_log_prob_ess'])
 def test_inversion_refusals(method):
-    m = fitted_on_host()
+    m = fitted_on_host(60)
     f = getattr(m, method)
     with pytest.raises(ValueError, match='no samples'):
         f(discard=60)

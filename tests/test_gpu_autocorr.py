@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from bisip_amd.autocorr import AutocorrError, _acf, auto_window, integrated_time
+from chain_harness import GuardedCall, used_window
 
 pytestmark = pytest.mark.gpu
 
@@ -56,16 +57,15 @@ def assert_tau_close(got, want, margin=None):
 
 
 def entry_point(t, n, first, stride, E, Wp, ndim, c=5.0):
-    """tau and windows from the C entry point on a device tensor, by pointer offset and stride (doubles)."""
+    """tau and windows from the C entry point on a device tensor, by pointer offset and stride (doubles).  Outputs and
+    workspace are followed by guard values."""
     import torch
     from bisip_amd import _hip
-    work = torch.empty(_hip.chain_autocorr_time_workspace(n, E, Wp, ndim), dtype=torch.uint8, device='cuda')
-    tau = torch.empty((E, ndim), dtype=torch.float64, device='cuda')
-    win = torch.empty((E, ndim), dtype=torch.int64, device='cuda')
-    _hip.chain_autocorr_time_dev(t.data_ptr() + 8 * first, n, stride, E, Wp, ndim, c, tau.data_ptr(),
-                                 win.data_ptr(), work.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return tau.cpu().numpy(), win.cpu().numpy()
+    call = GuardedCall()
+    tau, win = call.out('tau', (E, ndim)), call.out('the windows', (E, ndim), torch.int64)
+    work = call.work(_hip.chain_autocorr_time_workspace(n, E, Wp, ndim))
+    _hip.chain_autocorr_time_dev(t.data_ptr() + 8 * first, n, stride, E, Wp, ndim, c, tau, win, work, call.stream)
+    return tuple(call.finish())
 
 
 # a covering set of E in {1, 3, 64}, Wp in {2, 31, 256}, ndim in {1, 7, 12}, n_t in {1, 2, 3, 64, 1000, 5000}
@@ -87,10 +87,10 @@ def test_entry_point_against_emcee(E, Wp, ndim, n_t, discard, thin):
     rho = np.linspace(0.0, 0.95, ndim)
     full = ar1(rng, discard + n_t * thin, E * Wp, rho)
     t = torch.from_numpy(full).cuda()
-    first = discard + thin - 1
-    used = full[first::thin]
-    assert used.shape[0] == n_t
-    tau, win = entry_point(t, n_t, first * E * Wp * ndim, thin * E * Wp * ndim, E, Wp, ndim)
+    offset, stride, n = used_window(full.shape[0], E * Wp * ndim, discard, thin)
+    used = full[discard + thin - 1::thin]
+    assert used.shape[0] == n == n_t
+    tau, win = entry_point(t, n_t, offset, stride, E, Wp, ndim)
     want, want_win, margin = host_reference(used, E)
     assert_tau_close(tau, want, margin)
     assert np.array_equal(win, want_win)

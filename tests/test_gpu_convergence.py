@@ -7,12 +7,11 @@ import functools
 import numpy as np
 import pytest
 
+import fitted
+from chain_harness import SENTINEL, GuardedCall, assert_same_bits, shape_id, store
 from convergence_bounds import assert_within_bounds, hand_built_chain, reference_and_bounds
 
 pytestmark = pytest.mark.gpu
-
-DISCARD, THIN, PAD = 1, 2, 5       # every shape is read through an offset, a stride of two samples and padded samples
-SENTINEL = -7.25
 
 # (n, E, Wp, ndim).  Small columns counts are cut into segments of 32 samples (convergence.segment_plan): n = 64, 65 have
 # halves of one segment, 66 and 67 of two (the second of one sample), 129 and 130 of two and three.  (9, 256, 3, 2) is the
@@ -26,47 +25,34 @@ SHAPES = [(4, 1, 2, 1), (5, 3, 2, 2), (7, 2, 63, 7), (7, 2, 64, 7), (7, 2, 65, 7
 
 @functools.lru_cache(maxsize=None)
 def case(n, E, Wp, ndim):
-    """(stored samples, used chain (n, E * Wp, ndim), {split: (ordered mean, var, rhat)}, {split: reference and bounds})"""
+    """(store() of the chain, used chain (n, E * Wp, ndim), {split: (ordered mean, var, rhat)}, {split: reference and
+    bounds})"""
     from bisip_amd import convergence as cv
     x, centre, width = hand_built_chain(n, E, Wp, ndim)
-    row = E * Wp * ndim
-    stored = np.full((DISCARD + THIN * n, row + PAD), 1e6)          # what lies between the used samples is not read
-    stored[DISCARD + THIN - 1::THIN, :row] = x.reshape(n, row)
-    stored[:, row:] = np.nan
+    stored = store(x)
     ordered = {s: cv.ordered_rhat(x, s, n_ensembles=E) for s in (True, False)}
     ref = {s: reference_and_bounds(x, E, s) for s in (True, False)}
     x.setflags(write=False)
     return stored, x, ordered, ref
 
 
-def run_abi(stored, n, E, Wp, ndim, splits, mean=True, var=True, rhat=True, guard=64):
-    """One call; outputs not asked for stay SENTINEL.  The workspace is followed by ``guard`` bytes of 0xA5 that must
-    come back untouched."""
+def run_abi(stored, n, E, Wp, ndim, splits, mean=True, var=True, rhat=True):
+    """One call; outputs not asked for stay SENTINEL.  Outputs and workspace are followed by guard values."""
     import torch
     from bisip_amd import _hip
-    t = torch.from_numpy(stored).cuda()
-    stride = stored.shape[1]
-    m = torch.full((splits, E, Wp, ndim), SENTINEL, dtype=torch.float64, device='cuda')
-    v = torch.full((splits, E, Wp, ndim), SENTINEL, dtype=torch.float64, device='cuda')
-    r = torch.full((E, ndim), SENTINEL, dtype=torch.float64, device='cuda')
+    samples, offset, stride = stored
+    t = torch.from_numpy(samples).cuda()
+    call = GuardedCall()
+    m = call.out('the mean', (splits, E, Wp, ndim), asked=mean)
+    v = call.out('the variance', (splits, E, Wp, ndim), asked=var)
+    r = call.out('R-hat', (E, ndim), asked=rhat)
     nbytes = _hip.chain_rhat_workspace(n, E, Wp, ndim, splits)
-    assert nbytes >= 0
-    work = torch.full((nbytes + guard,), 0xA5, dtype=torch.uint8, device='cuda')
-    _hip.chain_rhat_dev(t.data_ptr() + 8 * (DISCARD + THIN - 1) * stride, n, THIN * stride, E, Wp, ndim, splits,
-                        m.data_ptr() if mean else 0, v.data_ptr() if var else 0, r.data_ptr() if rhat else 0,
-                        work.data_ptr() if nbytes else 0, nbytes, torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    assert (work[nbytes:] == 0xA5).all(), 'bytes after the workspace were written'
-    return m.cpu().numpy(), v.cpu().numpy(), r.cpu().numpy(), nbytes
+    _hip.chain_rhat_dev(t.data_ptr() + 8 * offset, n, stride, E, Wp, ndim, splits, m, v, r, call.work(nbytes), nbytes,
+                        call.stream)
+    return (*call.finish(), nbytes)
 
 
-def assert_same_bits(got, want, what):
-    fin = np.isfinite(want)
-    np.testing.assert_array_equal(np.isfinite(got), fin, err_msg=what)
-    np.testing.assert_array_equal(got[fin].view(np.uint64), want[fin].view(np.uint64), err_msg=what)
-
-
-@pytest.mark.parametrize('shape', SHAPES, ids=lambda s: 'x'.join(map(str, s)))
+@pytest.mark.parametrize('shape', SHAPES, ids=shape_id)
 def test_entry_point(shape):
     from bisip_amd import convergence as cv
     n, E, Wp, ndim = shape
@@ -103,7 +89,7 @@ def test_entry_point(shape):
         assert np.isfinite(r[:, 0]).all()
 
 
-@pytest.mark.parametrize('shape', [(7, 2, 65, 7), (67, 1, 5, 3), (9, 256, 3, 2)], ids=lambda s: 'x'.join(map(str, s)))
+@pytest.mark.parametrize('shape', [(7, 2, 65, 7), (67, 1, 5, 3), (9, 256, 3, 2)], ids=shape_id)
 def test_null_outputs_and_repeat(shape):
     """Every combination of outputs gives the bits of the full call and leaves the others alone; twice the same bits."""
     n, E, Wp, ndim = shape
@@ -162,11 +148,7 @@ def check_against_definitions(chain, lp, rhat_of, mean, std, lp_rhat_of, E):
 
 @pytest.mark.parametrize('where', ['device', 'host'])
 def test_model_methods(where):
-    import bisip_amd
-    m = bisip_amd.PolynomialDecomposition(bisip_amd.DataFiles()['SIP-K389175'], poly_deg=2, nwalkers=32, nsteps=40)
-    np.random.seed(4)
-    m.fit(chain=where)
-    assert m._sampler.chain_on_device == (where == 'device')
+    m = fitted.fitted_model(where, nsteps=40)
     for kw in (dict(discard=10, thin=3), dict()):
         chain, lp = m.get_chain(**kw), m._sampler.get_log_prob(**kw)
         assert m.get_rhat(**kw).shape == (m.ndim,) and m.get_walker_mean(**kw).shape == (32, m.ndim)

@@ -8,16 +8,15 @@ import functools
 import numpy as np
 import pytest
 
+import fitted
+from chain_harness import SENTINEL, GuardedCall, assert_same_bits, shape_id, store
 from convergence_bounds import U, hand_built_chain
 from covariance_bounds import assert_within, reference_and_bounds
 from moments_bounds import assert_within_bounds as assert_moments_within, reference_and_bounds as moments_reference
 
 pytestmark = pytest.mark.gpu
 
-DISCARD, THIN, PAD = 1, 2, 5       # every shape is read through an offset, a stride of two samples and padded samples
 LP_PAD = 3                         # the log-probability has a padding of its own
-SENTINEL = -7.25
-GUARD = 8                          # doubles after every output that must come back untouched
 
 # (n, E, Wp, ndim).  Rows N = n * Wp are cut into segments of 1024 at least (covariance.plan) and tiles of T = 256 (ndim
 # <= 8) or 64 rows: (204 | 205, 1, 5, q) have 1020 | 1025 rows, one segment | two with the second of one row, for both T;
@@ -30,65 +29,32 @@ SHAPES = [(1, 1, 2, 1), (5, 3, 2, 2), (40, 1, 1, 2), (7, 2, 63, 7), (7, 2, 64, 7
           (3, 256, 700, 7), (5, 256, 128, 16), (5000, 1, 32, 7), (600, 64, 64, 7)]
 
 
-def store(x, pad):
-    """Used samples x (n, row) as every second of the stored samples after DISCARD, with NaN padding columns."""
-    n, row = x.shape
-    stored = np.full((DISCARD + THIN * n, row + pad), 1e6)          # what lies between the used samples is not read
-    stored[DISCARD + THIN - 1::THIN, :row] = x
-    stored[:, row:] = np.nan
-    return stored
-
-
 @functools.lru_cache(maxsize=None)
 def case(n, E, Wp, ndim):
-    """(stored samples, used chain (n, E * Wp, ndim), ordered (mean, cov), reference and bounds)"""
+    """(store() of the chain, used chain (n, E * Wp, ndim), ordered (mean, cov), reference and bounds)"""
     from bisip_amd import covariance as cv
     x, _, _ = hand_built_chain(n, E, Wp, ndim)
-    stored = store(x.reshape(n, -1), PAD)
+    stored = store(x)
     ordered = cv.ordered_cov(x, n_ensembles=E)
     ref = reference_and_bounds(x, E)
     x.setflags(write=False)
     return stored, x, ordered, ref
 
 
-def guarded(shape, dtype=None, fill=SENTINEL):
-    import torch
-    size = int(np.prod(shape))
-    t = torch.full((size + GUARD,), fill, dtype=dtype or torch.float64, device='cuda')
-    return t
-
-
-def split_guard(t, shape, what, fill=SENTINEL):
-    size = int(np.prod(shape))
-    assert (t[size:] == fill).all(), f'doubles after {what} were written'
-    return t[:size].reshape(shape).cpu().numpy()
-
-
 def run_cov(stored, n, E, Wp, ndim, mean=True):
     """One call; a mean not asked for stays SENTINEL.  Outputs and workspace are followed by guard bytes."""
     import torch
     from bisip_amd import _hip
-    t = torch.from_numpy(stored).cuda()
-    stride = stored.shape[1]
-    m, c = guarded((E, ndim)), guarded((E, ndim, ndim))
+    samples, offset, stride = stored
+    t = torch.from_numpy(samples).cuda()
+    call = GuardedCall()
+    m, c = call.out('the mean', (E, ndim), asked=mean), call.out('the covariance', (E, ndim, ndim))
     nbytes = _hip.chain_cov_workspace(n, E, Wp, ndim)
-    assert nbytes >= 0
-    work = torch.full((nbytes + 64,), 0xA5, dtype=torch.uint8, device='cuda')
-    _hip.chain_cov_dev(t.data_ptr() + 8 * (DISCARD + THIN - 1) * stride, n, THIN * stride, E, Wp, ndim,
-                       m.data_ptr() if mean else 0, c.data_ptr(), work.data_ptr() if nbytes else 0, nbytes,
-                       torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    assert (work[nbytes:] == 0xA5).all(), 'bytes after the workspace were written'
-    return split_guard(m, (E, ndim), 'the mean'), split_guard(c, (E, ndim, ndim), 'the covariance'), nbytes
+    _hip.chain_cov_dev(t.data_ptr() + 8 * offset, n, stride, E, Wp, ndim, m, c, call.work(nbytes), nbytes, call.stream)
+    return (*call.finish(), nbytes)
 
 
-def assert_same_bits(got, want, what):
-    fin = np.isfinite(want)
-    np.testing.assert_array_equal(np.isfinite(got), fin, err_msg=what)
-    np.testing.assert_array_equal(got[fin].view(np.uint64), want[fin].view(np.uint64), err_msg=what)
-
-
-@pytest.mark.parametrize('shape', SHAPES, ids=lambda s: 'x'.join(map(str, s)))
+@pytest.mark.parametrize('shape', SHAPES, ids=shape_id)
 def test_cov_entry_point(shape):
     from bisip_amd import covariance as cv
     n, E, Wp, ndim = shape
@@ -120,7 +86,7 @@ def test_cov_entry_point(shape):
     assert np.isfinite(c[:, 0, 0]).all() and (c[:, 0, 0] >= 0).all()
 
 
-@pytest.mark.parametrize('shape', [(7, 2, 65, 7), (205, 1, 5, 9), (9, 256, 3, 2)], ids=lambda s: 'x'.join(map(str, s)))
+@pytest.mark.parametrize('shape', [(7, 2, 65, 7), (205, 1, 5, 9), (9, 256, 3, 2)], ids=shape_id)
 def test_cov_null_mean_and_repeat(shape):
     n, E, Wp, ndim = shape
     stored = case(*shape)[0]
@@ -133,7 +99,7 @@ def test_cov_null_mean_and_repeat(shape):
     np.testing.assert_array_equal(m1.view(np.uint64), m.view(np.uint64))
 
 
-@pytest.mark.parametrize('shape', [(50, 2, 8, 4), (300, 2, 8, 4), (40, 2, 8, 10)], ids=lambda s: 'x'.join(map(str, s)))
+@pytest.mark.parametrize('shape', [(50, 2, 8, 4), (300, 2, 8, 4), (40, 2, 8, 10)], ids=shape_id)
 def test_cov_known_answers(shape):
     """A constant parameter: exact zeros and NaN correlation.  A parameter that is twice another (its shift too): twice
     the sums, bit for bit.  A NaN in one parameter of one ensemble: that row and column of that ensemble and nothing else."""
@@ -143,7 +109,7 @@ def test_cov_known_answers(shape):
     x = rng.normal(size=(n, E * Wp, ndim)) * 0.01 + rng.normal(size=ndim)
     x[:, :Wp, 1] = 0.25
     x[:, :, 3] = 2.0 * x[:, :, 2]
-    m, c, _ = run_cov(store(x.reshape(n, -1), PAD), n, E, Wp, ndim)
+    m, c, _ = run_cov(store(x), n, E, Wp, ndim)
     assert (c[0, 1, :] == 0.0).all() and (c[0, :, 1] == 0.0).all() and (m[0, 1] == 0.25)
     corr = cv.corr_from_cov(c)
     assert np.isnan(corr[0, 1, :]).all() and np.isnan(corr[0, :, 1]).all()
@@ -156,7 +122,7 @@ def test_cov_known_answers(shape):
     for bad in (np.nan, np.inf, -np.inf):
         y = x.copy()
         y[n // 2, Wp + 3, 2] = bad
-        _, cb, _ = run_cov(store(y.reshape(n, -1), PAD), n, E, Wp, ndim)
+        _, cb, _ = run_cov(store(y), n, E, Wp, ndim)
         spoilt = np.zeros((E, ndim, ndim), dtype=bool)
         spoilt[1, 2, :] = spoilt[1, :, 2] = True
         np.testing.assert_array_equal(~np.isfinite(cb), spoilt)
@@ -193,24 +159,18 @@ def run_best(x, lp, E, theta=True, best=True, index=True):
     Wp = W // E
     if _uploaded.get('id') != id(x):                    # (the chain of a test goes up once)
         _uploaded.clear()
-        _uploaded.update(id=id(x), x=x, t=torch.from_numpy(store(x.reshape(n, -1), PAD)).cuda())
-    sl = store(lp, LP_PAD)
-    tx, tl = _uploaded['t'], torch.from_numpy(sl).cuda()
-    cstride = tx.shape[1]
-    th, b = guarded((E, ndim)), guarded((E,))
-    ix = guarded((E,), torch.int64, -7)
+        stored, offset, stride = store(x)
+        _uploaded.update(id=id(x), x=x, chain=(torch.from_numpy(stored).cuda(), offset, stride))
+    tx, coffset, cstride = _uploaded['chain']
+    sl, loffset, lstride = store(lp, pad=LP_PAD)
+    tl = torch.from_numpy(sl).cuda()
+    call = GuardedCall()
+    th, b = call.out('theta', (E, ndim), asked=theta), call.out('the log-probability', (E,), asked=best)
+    ix = call.out('the index', (E,), torch.int64, asked=index)
     nbytes = _hip.chain_best_sample_workspace(n, E, Wp)
-    assert nbytes >= 0
-    work = torch.full((nbytes + 64,), 0xA5, dtype=torch.uint8, device='cuda')
-    first = DISCARD + THIN - 1
-    _hip.chain_best_sample_dev(tx.data_ptr() + 8 * first * cstride if theta else 0, THIN * cstride,
-                               tl.data_ptr() + 8 * first * sl.shape[1], THIN * sl.shape[1], n, E, Wp, ndim,
-                               th.data_ptr() if theta else 0, b.data_ptr() if best else 0, ix.data_ptr() if index else 0,
-                               work.data_ptr() if nbytes else 0, nbytes, torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    assert (work[nbytes:] == 0xA5).all(), 'bytes after the workspace were written'
-    return (split_guard(th, (E, ndim), 'theta'), split_guard(b, (E,), 'the log-probability'),
-            split_guard(ix, (E,), 'the index', -7))
+    _hip.chain_best_sample_dev(tx.data_ptr() + 8 * coffset if theta else 0, cstride, tl.data_ptr() + 8 * loffset, lstride,
+                               n, E, Wp, ndim, th, b, ix, call.work(nbytes), nbytes, call.stream)
+    return tuple(call.finish())
 
 
 def numpy_best(x, lp, E):
@@ -238,7 +198,7 @@ BEST_SHAPES = [(1, 1, 1, 1), (7, 2, 65, 7), (819, 1, 5, 3), (820, 1, 5, 3), (9, 
 # keys (k_best_merge), whose lanes 0 and 1 then take a second segment each
 
 
-@pytest.mark.parametrize('shape', BEST_SHAPES, ids=lambda s: 'x'.join(map(str, s)))
+@pytest.mark.parametrize('shape', BEST_SHAPES, ids=shape_id)
 def test_best_sample_entry_point(shape):
     from bisip_amd import covariance as cv
     n, E, Wp, ndim = shape
@@ -277,7 +237,7 @@ def test_best_sample_entry_point(shape):
     assert assert_best(x, y, E, 'all NaN')[e] == 0
 
 
-@pytest.mark.parametrize('shape', [(7, 2, 65, 7), (820, 1, 5, 3)], ids=lambda s: 'x'.join(map(str, s)))
+@pytest.mark.parametrize('shape', [(7, 2, 65, 7), (820, 1, 5, 3)], ids=shape_id)
 def test_best_sample_null_outputs(shape):
     n, E, Wp, ndim = shape
     rng = np.random.default_rng(3)
@@ -297,14 +257,7 @@ def test_best_sample_null_outputs(shape):
 KW = dict(discard=20, thin=2)
 
 
-@functools.lru_cache(maxsize=None)
-def fitted_model(where):
-    import bisip_amd
-    m = bisip_amd.PolynomialDecomposition(bisip_amd.DataFiles()['SIP-K389175'], poly_deg=2, nwalkers=32, nsteps=120)
-    np.random.seed(4)
-    m.fit(chain=where)
-    assert m._sampler.chain_on_device == (where == 'device')
-    return m
+fitted_model = functools.lru_cache(maxsize=None)(fitted.fitted_model)
 
 
 def check_layers(chain, lp, cov, corr, std, theta, best, logp_of, E):

@@ -11,6 +11,7 @@ import warnings
 import numpy as np
 import pytest
 
+from chain_harness import GuardedCall
 from test_decomposition import (DEBYE_TUTORIAL, TOTAL_M_RECORDED, U, assert_within, bounds, prior_rows,
                                 yardstick)
 
@@ -47,11 +48,10 @@ def chain_columns(t, n, off, stride, E, Wp, ndim, log_tau):
     from bisip_amd import _hip
     L = len(log_tau)
     lt = torch.from_numpy(np.ascontiguousarray(log_tau)).cuda()
-    cols = torch.empty((E * L, n * Wp), dtype=torch.float64, device='cuda')
-    _hip.rtd_columns_dev(t.data_ptr() + 8 * off, n, stride, E, Wp, ndim, 0, E, lt.data_ptr(), L, cols.data_ptr(),
-                         torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return cols.cpu().numpy().reshape(E, L, n * Wp)
+    call = GuardedCall()
+    cols = call.out('the columns', (E, L, n * Wp))
+    _hip.rtd_columns_dev(t.data_ptr() + 8 * off, n, stride, E, Wp, ndim, 0, E, lt.data_ptr(), L, cols, call.stream)
+    return call.finish()[0]
 
 
 def rtd_columns(s, log_tau, discard, thin):

@@ -10,11 +10,9 @@ import pytest
 
 import ess_cases as ec
 from bisip_amd import ess as es
+from chain_harness import SENTINEL, GuardedCall, used_window
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = -7.25
-GUARD = 64
 
 
 def on_device(case):
@@ -23,23 +21,21 @@ def on_device(case):
     import torch
     E, Wp, ndim, n, discard, thin = case
     stored = ec.cover_case(*case)[0]
-    width = stored.shape[1]
-    return torch.from_numpy(stored.copy()).cuda(), (discard + thin - 1) * width, thin * width
+    offset, stride, used = used_window(stored.shape[0], stored.shape[1], discard, thin)
+    assert used == n
+    return torch.from_numpy(stored.copy()).cuda(), offset, stride
 
 
 def run_rank(t, offset, stride, n, E, Wp, ndim):
-    """One bisip_chain_rank_normalize_dev call; the workspace is followed by GUARD bytes that must come back untouched."""
-    import torch
+    """One bisip_chain_rank_normalize_dev call; output and workspace are followed by guard values."""
     from bisip_amd import _hip
     nbytes = _hip.chain_rank_normalize_workspace(n, E, Wp, ndim)
     assert nbytes > 0
-    work = torch.full((nbytes + GUARD,), 0xA5, dtype=torch.uint8, device='cuda')
-    z = torch.full((n, E * Wp, ndim), SENTINEL, dtype=torch.float64, device='cuda')
-    _hip.chain_rank_normalize_dev(t.data_ptr() + 8 * offset, n, stride, E, Wp, ndim, z.data_ptr(), work.data_ptr(), nbytes,
-                                  torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    assert (work[nbytes:] == 0xA5).all(), 'bytes after the workspace were written'
-    return z.cpu().numpy()
+    call = GuardedCall()
+    z = call.out('z', (n, E * Wp, ndim))
+    _hip.chain_rank_normalize_dev(t.data_ptr() + 8 * offset, n, stride, E, Wp, ndim, z, call.work(nbytes), nbytes,
+                                  call.stream)
+    return call.finish()[0]
 
 
 def run_ess(t, offset, stride, n, E, Wp, ndim, splits, thr=None):
@@ -49,14 +45,12 @@ def run_ess(t, offset, stride, n, E, Wp, ndim, splits, thr=None):
     T = 0 if thr is None else thr.shape[0]
     nbytes = _hip.chain_ess_workspace(n, E, Wp, ndim, splits, T)
     assert nbytes > 0
-    work = torch.full((nbytes + GUARD,), 0xA5, dtype=torch.uint8, device='cuda')
-    out = torch.full((max(1, T), E, ndim), SENTINEL, dtype=torch.float64, device='cuda')
+    call = GuardedCall()
+    out = call.out('the effective sample sizes', (max(1, T), E, ndim))
     d_thr = torch.from_numpy(np.ascontiguousarray(thr)).cuda() if T else None
     _hip.chain_ess_dev(t.data_ptr() + 8 * offset, n, stride, E, Wp, ndim, splits, d_thr.data_ptr() if T else 0, T,
-                       out.data_ptr(), work.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    assert (work[nbytes:] == 0xA5).all(), 'bytes after the workspace were written'
-    res = out.cpu().numpy()
+                       out, call.work(nbytes), nbytes, call.stream)
+    res = call.finish()[0]
     assert not (res == SENTINEL).any()
     return res if T else res[0]
 

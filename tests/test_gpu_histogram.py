@@ -7,6 +7,8 @@ import warnings
 import numpy as np
 import pytest
 
+from chain_harness import GuardedCall, used_window
+
 pytestmark = pytest.mark.gpu
 
 
@@ -32,33 +34,31 @@ def flat_of(host, e, Wp):
 
 
 def abi_counts(t, offset, n, stride, E, Wp, ndim, edges):
-    """Both entry points on device tensor t: (counts (E, ndim, bins), pair counts (E, npairs, bins, bins))."""
+    """Both entry points on device tensor t: (counts (E, ndim, bins), pair counts (E, npairs, bins, bins)).  The counts
+    start as -7 (the call must clear them) and are followed by guard values."""
     import torch
     from bisip_amd import _hip
     bins = edges.shape[2] - 1
-    st = torch.cuda.current_stream().cuda_stream
     d_edges = torch.from_numpy(np.ascontiguousarray(edges)).cuda()
-    counts = torch.full((E, ndim, bins), -7, dtype=torch.int64, device='cuda')          # the call must clear them
-    _hip.chain_histograms_dev(t.data_ptr() + 8 * offset, n, stride, E, Wp, ndim, d_edges.data_ptr(), bins,
-                              counts.data_ptr(), st)
-    pairs = None
+    call = GuardedCall()
+    counts = call.out('the counts', (E, ndim, bins), torch.int64)
+    _hip.chain_histograms_dev(t.data_ptr() + 8 * offset, n, stride, E, Wp, ndim, d_edges.data_ptr(), bins, counts,
+                              call.stream)
     if ndim >= 2:
-        pairs = torch.full((E, ndim * (ndim - 1) // 2, bins, bins), -7, dtype=torch.int64, device='cuda')
-        _hip.chain_pair_histograms_dev(t.data_ptr() + 8 * offset, n, stride, E, Wp, ndim, d_edges.data_ptr(), bins,
-                                       pairs.data_ptr(), st)
-    torch.cuda.synchronize()
-    return counts.cpu().numpy(), None if pairs is None else pairs.cpu().numpy()
+        pairs = call.out('the pair counts', (E, ndim * (ndim - 1) // 2, bins, bins), torch.int64)
+        _hip.chain_pair_histograms_dev(t.data_ptr() + 8 * offset, n, stride, E, Wp, ndim, d_edges.data_ptr(), bins, pairs,
+                                       call.stream)
+    got = call.finish()
+    return got[0], got[1] if ndim >= 2 else None
 
 
 def abi_range(t, offset, n, stride, E, Wp, ndim):
     import torch
     from bisip_amd import _hip
-    out = torch.empty((E, ndim, 2), dtype=torch.float64, device='cuda')
-    bad = torch.full((E, ndim), -7, dtype=torch.int64, device='cuda')
-    _hip.chain_range_dev(t.data_ptr() + 8 * offset, n, stride, E, Wp, ndim, out.data_ptr(), bad.data_ptr(),
-                         torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return out.cpu().numpy(), bad.cpu().numpy()
+    call = GuardedCall()
+    out, bad = call.out('the range', (E, ndim, 2)), call.out('the count of non-finite values', (E, ndim), torch.int64)
+    _hip.chain_range_dev(t.data_ptr() + 8 * offset, n, stride, E, Wp, ndim, out, bad, call.stream)
+    return tuple(call.finish())
 
 
 def hand_built_chain(E, Wp, ndim, bins, stored, seed):
@@ -117,11 +117,10 @@ def test_entry_points_equal_numpy(hip_lib, E, Wp, ndim, bins, stored, discard, t
     pad = 5
     t = torch.full((pad + stored * W * ndim + pad,), float('nan'), dtype=torch.float64, device='cuda')
     t[pad:pad + stored * W * ndim] = torch.from_numpy(host.reshape(-1)).cuda()
-    first = discard + thin - 1
-    used = host[first::thin]
-    n = used.shape[0]
-    assert n >= 2
-    offset, stride = pad + first * W * ndim, thin * W * ndim
+    offset, stride, n = used_window(stored, W * ndim, discard, thin)
+    offset += pad
+    used = host[discard + thin - 1::thin]
+    assert used.shape[0] == n >= 2
     counts, pairs = abi_counts(t, offset, n, stride, E, Wp, ndim, edges)
     minmax, bad = abi_range(t, offset, n, stride, E, Wp, ndim)
     r = np.stack([edges[..., 0], edges[..., -1]], axis=-1)

@@ -7,13 +7,12 @@ import functools
 import numpy as np
 import pytest
 
+import fitted
+from chain_harness import SENTINEL, GuardedCall, shape_id, store
 from convergence_bounds import hand_built_chain
 
 pytestmark = pytest.mark.gpu
 
-DISCARD, THIN, PAD = 1, 2, 5       # every shape is read through an offset, a stride of two samples and padded samples
-SENTINEL = -7.25
-GUARD = 8                          # values after every output that must come back untouched
 MASSES = (0.5, 0.9, 0.95)
 
 # (n, E, Wp, ndim).  (1, 1, 2 | 3, 1): N = 2 and 3, M = 1.  (255 | 256 | 257, 1, 1, 2) and (1023 | 1024 | 1025, 1, 1, 1): on
@@ -27,23 +26,20 @@ SHAPES = [(1, 1, 2, 1), (1, 1, 3, 1), (5, 3, 2, 2), (255, 1, 1, 2), (256, 1, 1, 
           (8200, 1, 1, 3), (41000, 1, 1, 2), (4095, 1, 1, 2), (4096, 1, 1, 2), (600, 64, 64, 7)]
 
 
-def store(x, pad):
-    """Used samples x (n, row) as every second of the stored samples after DISCARD, with NaN padding columns."""
-    n, row = x.shape
-    stored = np.full((DISCARD + THIN * n, row + pad), 1e6)          # what lies between the used samples is not read
-    stored[DISCARD + THIN - 1::THIN, :row] = x
-    stored[:, row:] = np.nan
-    return stored
+def on_device(x):
+    """store() of x (n, E * Wp, ndim) with the samples on the device: what run_hdi takes as ``t``."""
+    import torch
+    stored, offset, stride = store(x)
+    return torch.from_numpy(stored).cuda(), offset, stride
 
 
 @functools.lru_cache(maxsize=3)
 def case(n, E, Wp, ndim):
     """(stored samples on the device, the definition's (intervals, indices) for MASSES): computed once per shape."""
-    import torch
     from bisip_amd import interval as iv
     x, _, _ = hand_built_chain(n, E, Wp, ndim)
     want = iv.hdi(x, MASSES, E, index=True)
-    return torch.from_numpy(store(x.reshape(n, -1), PAD)).cuda(), want
+    return on_device(x), want
 
 
 def run_hdi(t, n, E, Wp, ndim, K, path, monkeypatch, index=True):
@@ -55,22 +51,15 @@ def run_hdi(t, n, E, Wp, ndim, K, path, monkeypatch, index=True):
     else:
         monkeypatch.setenv('BISIP_HDI_PATH', path)
     K = [int(k) for k in K]
-    stride = t.shape[1]
-    size, isize = len(K) * 2 * E * ndim, len(K) * E * ndim
-    out = torch.full((size + GUARD,), SENTINEL, dtype=torch.float64, device='cuda')
-    idx = torch.full((isize + GUARD,), -7, dtype=torch.int64, device='cuda')
+    samples, offset, stride = t
+    call = GuardedCall()
+    out = call.out('the intervals', (len(K), 2, E, ndim))
+    idx = call.out('the indices', (len(K), E, ndim), torch.int64, asked=index)
     nbytes = _hip.chain_hdi_workspace(n, E, Wp, ndim, K)
     assert nbytes > 0
-    work = torch.full((nbytes + 64,), 0xA5, dtype=torch.uint8, device='cuda')
-    _hip.chain_hdi_dev(t.data_ptr() + 8 * (DISCARD + THIN - 1) * stride, n, THIN * stride, E, Wp, ndim, K, out.data_ptr(),
-                       idx.data_ptr() if index else 0, work.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    assert (work[nbytes:] == 0xA5).all(), 'bytes after the workspace were written'
-    assert (out[size:] == SENTINEL).all(), 'doubles after the intervals were written'
-    assert (idx[isize:] == -7).all(), 'values after the indices were written'
-    if not index:
-        assert (idx == -7).all()
-    return out[:size].reshape(len(K), 2, E, ndim).cpu().numpy(), idx[:isize].reshape(len(K), E, ndim).cpu().numpy(), nbytes
+    _hip.chain_hdi_dev(samples.data_ptr() + 8 * offset, n, stride, E, Wp, ndim, K, out, idx, call.work(nbytes), nbytes,
+                       call.stream)
+    return (*call.finish(), nbytes)
 
 
 def assert_equal(got, want, what):
@@ -83,7 +72,7 @@ def assert_equal(got, want, what):
     np.testing.assert_array_equal(gi, wi, err_msg=what)
 
 
-@pytest.mark.parametrize('shape', SHAPES, ids=lambda s: 'x'.join(map(str, s)))
+@pytest.mark.parametrize('shape', SHAPES, ids=shape_id)
 def test_hdi_entry_point(shape, monkeypatch):
     from bisip_amd import interval as iv
     n, E, Wp, ndim = shape
@@ -105,7 +94,7 @@ def test_hdi_entry_point(shape, monkeypatch):
         assert np.isnan(lo).any() and not np.isnan(lo).all()          # hand_built_chain planted NaNs, in some columns only
 
 
-@pytest.mark.parametrize('shape', [(4095, 1, 1, 2), (4096, 1, 1, 2), (600, 64, 64, 7)], ids=lambda s: 'x'.join(map(str, s)))
+@pytest.mark.parametrize('shape', [(4095, 1, 1, 2), (4096, 1, 1, 2), (600, 64, 64, 7)], ids=shape_id)
 def test_path_switch(shape, monkeypatch):
     """Without BISIP_HDI_PATH the rule of interval.plan decides: the workspace is that path's, the results the same."""
     from bisip_amd import interval as iv
@@ -150,8 +139,7 @@ def test_extreme_windows_and_null_index(path, monkeypatch):
     x[5, 0, 2] = x[900, 0, 2]                                        # a pair of width 0
     x[7, 0, 1] = -0.0
     x[8, 0, 1] = 0.0
-    import torch
-    t = torch.from_numpy(store(x.reshape(n, -1), PAD)).cuda()
+    t = on_device(x)
     K = [N - 1, 1]
     g, gi, _ = run_hdi(t, n, E, Wp, ndim, K, path, monkeypatch)
     for k, kk in enumerate(K):
@@ -165,7 +153,7 @@ def test_extreme_windows_and_null_index(path, monkeypatch):
     y = x.copy()
     y[:40, 0, 0] = -np.inf
     y[40:90, 0, 0] = np.inf
-    t = torch.from_numpy(store(y.reshape(n, -1), PAD)).cuda()
+    t = on_device(y)
     for mass in (0.01, 0.5, 0.98):
         got = run_hdi(t, n, E, Wp, ndim, iv.windows(mass, N), path, monkeypatch)
         assert_equal((got[0][0], got[1][0]), iv.hdi(y, mass, E, index=True), f'inf {mass} {path}')
@@ -190,14 +178,7 @@ def test_hdi_of_a_device_tensor(monkeypatch):
 KW = dict(discard=20, thin=2)
 
 
-@functools.lru_cache(maxsize=None)
-def fitted_model():
-    import bisip_amd
-    m = bisip_amd.PolynomialDecomposition(bisip_amd.DataFiles()['SIP-K389175'], poly_deg=2, nwalkers=32, nsteps=120)
-    np.random.seed(4)
-    m.fit(chain='device')
-    assert m._sampler.chain_on_device
-    return m
+fitted_model = functools.lru_cache(maxsize=None)(fitted.fitted_model)         # (where='device': asserted there)
 
 
 def test_model_methods(monkeypatch):

@@ -5,48 +5,32 @@ bound of any summation order that tests/moments_bounds.py derives and computes p
 import numpy as np
 import pytest
 
+import fitted
+from chain_harness import SENTINEL, GuardedCall, shape_id, store
 from moments_bounds import (BOTH_INFINITIES, EXTREMES, SHAPES, assert_agrees_with_numpy, assert_same_bits,
                             assert_within_bounds, case, has_extremes, reference_and_bounds)
 
 pytestmark = pytest.mark.gpu
 
-DISCARD, THIN, PAD = 1, 2, 5       # every shape is read through an offset, a stride of two samples and padded samples
-SENTINEL = -7.25
-GUARD = 64
-ids = dict(ids=lambda s: 'x'.join(map(str, s)))
+ids = dict(ids=shape_id)
 
 
-def stored_samples(x, discard=DISCARD, thin=THIN, pad=PAD):
-    """(stored (discard + thin * n, row + pad), index of the first used sample): the used samples of x at emcee's places,
-    1e6 in the samples between them (not read), NaN in the padding after every sample."""
-    n = x.shape[0]
-    row = x.shape[1] * x.shape[2]
-    stored = np.full((discard + thin * n, row + pad), 1e6)
-    stored[discard + thin - 1::thin, :row] = x.reshape(n, row)
-    stored[:, row:] = np.nan
-    return stored, discard + thin - 1
-
-
-def run_abi(x, E, discard=DISCARD, thin=THIN, pad=PAD):
-    """One call on x (n, E * Wp, ndim) through the storage above.  Outputs start as SENTINEL; the workspace holds exactly
-    chain_moments_workspace() doubles and is followed by GUARD bytes of 0xA5 that must come back untouched."""
+def run_abi(x, E, **storage):
+    """One call on x (n, E * Wp, ndim) through store(x, **storage).  Outputs start as SENTINEL; the workspace holds exactly
+    chain_moments_workspace() doubles; both are followed by guard values that must come back untouched."""
     import torch
     from bisip_amd import _hip
     from bisip_amd.chainview import moment_splits
     n, W, ndim = x.shape
-    stored, first = stored_samples(x, discard, thin, pad)
+    stored, offset, stride = store(x, **storage)
     t = torch.from_numpy(stored).cuda()
-    stride = stored.shape[1]
-    mean = torch.full((E, ndim), SENTINEL, dtype=torch.float64, device='cuda')
-    std = torch.full((E, ndim), SENTINEL, dtype=torch.float64, device='cuda')
+    call = GuardedCall()
+    mean, std = call.out('the mean', (E, ndim)), call.out('the std', (E, ndim))
     doubles = _hip.chain_moments_workspace(n, E, ndim)
     assert doubles == E * moment_splits(n, E) * ndim                  # as large as the header says and no larger
-    work = torch.full((8 * doubles + GUARD,), 0xA5, dtype=torch.uint8, device='cuda')
-    _hip.chain_moments_dev(t.data_ptr() + 8 * first * stride, n, thin * stride, E, W // E, ndim, mean.data_ptr(),
-                           std.data_ptr(), work.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    assert (work[8 * doubles:] == 0xA5).all(), 'bytes after the workspace were written'
-    return mean.cpu().numpy(), std.cpu().numpy()
+    _hip.chain_moments_dev(t.data_ptr() + 8 * offset, n, stride, E, W // E, ndim, mean, std, call.work(8 * doubles),
+                           call.stream)
+    return call.finish()
 
 
 def same_bits(a, b):
@@ -132,9 +116,8 @@ def test_device_moments_of_a_view_with_offset_and_stride_and_of_a_derived_one():
     n, E, Wp, ndim = 8, 5, 19, 13
     c = case(n, E, Wp, ndim)
     x = c['x']
-    stored, first = stored_samples(x)
-    stride = stored.shape[1]
-    view = ChainView(torch.from_numpy(stored).cuda(), n, E, Wp, ndim, offset=first * stride, stride=THIN * stride)
+    stored, offset, stride = store(x)
+    view = ChainView(torch.from_numpy(stored).cuda(), n, E, Wp, ndim, offset=offset, stride=stride)
     mean, std = device_moments(view)
     assert_same_bits(mean, c['ordered'][0], 'mean')
     assert_same_bits(std, c['ordered'][1], 'std')
@@ -164,11 +147,7 @@ def check_methods(chain, E, mean, std, device):
 
 @pytest.mark.parametrize('where', ['device', 'host'])
 def test_model_methods(where):
-    import bisip_amd
-    m = bisip_amd.PolynomialDecomposition(bisip_amd.DataFiles()['SIP-K389175'], poly_deg=2, nwalkers=32, nsteps=40)
-    np.random.seed(4)
-    m.fit(chain=where)
-    assert m._sampler.chain_on_device == (where == 'device')
+    m = fitted.fitted_model(where, nsteps=40)
     for kw in (dict(discard=10, thin=3), dict()):
         mean, std = m.get_param_mean(**kw), m.get_param_std(**kw)
         assert mean.shape == std.shape == (m.ndim,)

@@ -10,6 +10,7 @@ import functools
 import numpy as np
 import pytest
 
+from chain_harness import assert_same_bits, used_window
 from response_bounds import assert_within, reference_and_bounds
 
 pytestmark = pytest.mark.gpu
@@ -92,18 +93,11 @@ def forward_rows(b, used, first=0, count=None):
 
 def view_of(stored, discard, thin, n_ensembles, Wp, first=0, count=None):
     """The ChainView of the used samples of `count` ensembles starting with `first` of a stored chain tensor."""
-    from bisip_amd.chainview import ChainView, used_range
+    from bisip_amd.chainview import ChainView
     total, W, ndim = stored.shape
-    k0, n = used_range(total, discard, thin)
+    offset, stride, n = used_window(total, W * ndim, discard, thin)
     count = n_ensembles - first if count is None else count
-    row = W * ndim
-    return ChainView(stored, n, count, Wp, ndim, k0 * row + first * Wp * ndim, thin * row)
-
-
-def assert_same_bits(got, want, what):
-    fin = np.isfinite(want)
-    np.testing.assert_array_equal(np.isfinite(got), fin, err_msg=what)
-    np.testing.assert_array_equal(got[fin].view(np.uint64), want[fin].view(np.uint64), err_msg=what)
+    return ChainView(stored, n, count, Wp, ndim, offset + first * Wp * ndim, stride)
 
 
 def assert_pa_percentiles(got, Z, what):

@@ -9,10 +9,10 @@ import warnings
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+import fitted
+from chain_harness import SENTINEL, GuardedCall, shape_id, store
 
-DISCARD, THIN, PAD = 1, 2, 5       # every shape is read through an offset, a stride of two samples and padded samples
-SENTINEL = -7.25
+pytestmark = pytest.mark.gpu
 
 P_SETS = [[50.0], [0.0, 100.0], [2.5, 50.0, 97.5], [0.0, 2.5, 16.0, 33.3, 50.0, 84.0, 97.5, 100.0], None]
 
@@ -36,9 +36,8 @@ def shapes():
 
 @functools.lru_cache(maxsize=None)
 def hand_built_chain(n, E, Wp, ndim):
-    """The stored samples (stored, E * Wp * ndim + PAD) of a chain whose used samples (DISCARD, THIN) are (n, E, Wp,
-    ndim): columns of widths 1e-8 ... 1e2 around centres of any size, a constant column, duplicated values, and in
-    chosen (sample, ensemble, parameter) slices +NaN, -NaN, +inf, -inf and both infinities.  Returns (stored array, used
+    """store() of a chain whose used samples are (n, E, Wp, ndim), with a random filler between them: columns of widths 1e-8 ... 1e2 around centres of any size, a constant column, duplicated values, and in
+    chosen (sample, ensemble, parameter) slices +NaN, -NaN, +inf, -inf and both infinities.  Returns (store()'s three, used
     (n, E, Wp, ndim), mask of the slices with a non-finite value (n, E, ndim))."""
     rng = np.random.default_rng(n * 1000003 + E * 10007 + Wp * 101 + ndim)
     centre = rng.normal(size=(1, E, 1, ndim)) * 10.0 ** rng.integers(-3, 4, (1, E, 1, ndim))
@@ -59,30 +58,23 @@ def hand_built_chain(n, E, Wp, ndim):
     # -nan must really carry the sign bit
     neg = np.array([-np.nan])
     assert np.signbit(neg[0])
-    row = E * Wp * ndim
-    stored = rng.normal(size=(DISCARD + THIN * n, row + PAD)) * 1e6    # what lies between the used samples is not read
-    stored[DISCARD + THIN - 1::THIN, :row] = used.reshape(n, row)
-    stored[:, row:] = np.nan
-    return stored, used, bad
+    return store(used, filler=lambda shape: rng.normal(size=shape) * 1e6), used, bad
 
 
 def run_abi(stored, n, E, Wp, ndim, p, mean=True):
     import torch
     from bisip_amd import _hip
-    t = torch.from_numpy(stored).cuda()
-    stride = stored.shape[1]
+    samples, offset, stride = stored
+    t = torch.from_numpy(samples).cuda()
     n_p = 0 if p is None else len(p)
-    pct = torch.full((n_p, n, E, ndim), SENTINEL, dtype=torch.float64, device='cuda')
-    avg = torch.full((n, E, ndim), SENTINEL, dtype=torch.float64, device='cuda')
+    call = GuardedCall()
+    pct = call.out('the percentiles', (n_p, n, E, ndim), asked=n_p > 0)
+    avg = call.out('the mean', (n, E, ndim), asked=mean)
     nbytes = _hip.chain_trace_workspace(n, E, Wp, ndim, n_p)
-    assert nbytes >= 0
     assert (nbytes == 0) == (Wp <= lds_walkers(ndim))
-    work = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device='cuda')
-    _hip.chain_trace_dev(t.data_ptr() + 8 * (DISCARD + THIN - 1) * stride, n, THIN * stride, E, Wp, ndim, p,
-                         pct.data_ptr() if n_p else 0, avg.data_ptr() if mean else 0, work.data_ptr() if nbytes else 0,
-                         nbytes, torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return pct.cpu().numpy(), avg.cpu().numpy()
+    _hip.chain_trace_dev(t.data_ptr() + 8 * offset, n, stride, E, Wp, ndim, p, pct, avg, call.work(nbytes), nbytes,
+                         call.stream)
+    return call.finish()
 
 
 def fixed_order_mean(x):
@@ -125,7 +117,7 @@ def check_mean(got, used, bad):
     return worst
 
 
-@pytest.mark.parametrize('shape', shapes(), ids=lambda s: 'x'.join(map(str, s)))
+@pytest.mark.parametrize('shape', shapes(), ids=shape_id)
 def test_entry_point_against_numpy(shape):
     n, E, Wp, ndim = shape
     stored, used, bad = hand_built_chain(*shape)
@@ -154,12 +146,7 @@ def test_entry_point_against_numpy(shape):
 
 
 def fit_model(where):
-    import bisip_amd
-    m = bisip_amd.PolynomialDecomposition(bisip_amd.DataFiles()['SIP-K389175'], poly_deg=2, nwalkers=32, nsteps=40)
-    np.random.seed(4)
-    m.fit(chain=where)
-    assert m._sampler.chain_on_device == (where == 'device')
-    return m
+    return fitted.fitted_model(where, nsteps=40)
 
 
 def check_model(m, kw):

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from bisip_amd import histogram as hg
+from fitted import fitted_on_host
 
 BINS = [1, 2, 20, 25, 64]
 WIDTHS = [1e-8, 1e-5, 1e-2, 1.0, 1e2]
@@ -199,24 +200,6 @@ def test_sample_and_edge_shapes_are_checked():
 
 
 # -- the Inversion methods on a model fitted with the host sampler ------------------------------------------------
-def gaussian_logp(theta):
-    return -0.5 * np.sum((theta - np.array([1.0, 0.01, 0.0, 0.0])) ** 2 / 1e-4, axis=1)
-
-
-def fitted_on_host():
-    """A PolynomialDecomposition whose chain comes from the host sampler around a NumPy log-probability (the pattern of
-    tests/test_decomposition.py): nothing here touches the device."""
-    import bisip_amd
-    from bisip_amd.sampler import EnsembleSampler
-    m = bisip_amd.PolynomialDecomposition(bisip_amd.DataFiles()['SIP-K389175'], poly_deg=2, nwalkers=8)
-    np.random.seed(1)
-    s = EnsembleSampler(8, 4, gaussian_logp)
-    s.run_mcmc(np.array([1.0, 0.01, 0.0, 0.0]) + 1e-3 * np.random.randn(8, 4), 20)
-    m._sampler = s
-    m._Inversion__fitted = True
-    return m
-
-
 def range_kinds(m, flat):
     lo, hi = flat.min(axis=0), flat.max(axis=0)
     explicit = np.stack([lo + 0.25 * (hi - lo), hi - 0.25 * (hi - lo)], axis=1)     # cuts samples off on either side

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from bisip_amd import interval as iv
+from fitted import fitted_on_host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -232,22 +233,6 @@ def test_entry_point_checks_its_arguments(monkeypatch):
 
 
 # -- the methods ------------------------------------------------------------------------------------------------------
-def gaussian_logp(theta):
-    return -0.5 * np.sum((theta - np.array([1.0, 0.01, 0.0, 0.0])) ** 2 / 1e-4, axis=1)
-
-
-def fitted_on_host():
-    import bisip_amd
-    from bisip_amd.sampler import EnsembleSampler
-    m = bisip_amd.PolynomialDecomposition(bisip_amd.DataFiles()['SIP-K389175'], poly_deg=2, nwalkers=8)
-    np.random.seed(1)
-    s = EnsembleSampler(8, 4, gaussian_logp)
-    s.run_mcmc(np.array([1.0, 0.01, 0.0, 0.0]) + 1e-3 * np.random.randn(8, 4), 20)
-    m._sampler = s
-    m._Inversion__fitted = True
-    return m
-
-
 def test_model_method_with_the_host_sampler():
     m = fitted_on_host()
     kw = dict(discard=5, thin=3)

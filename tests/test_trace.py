@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from bisip_amd import trace as tr
+from fitted import fitted_on_host
 
 P_SETS = [[50], [0, 100], [2.5, 50, 97.5], [0, 2.5, 16, 33.3, 50, 84, 97.5, 100]]
 
@@ -69,24 +70,6 @@ def test_used_steps(n_total):
 
 
 # -- the Inversion methods on a model fitted with the host sampler ------------------------------------------------
-def gaussian_logp(theta):
-    return -0.5 * np.sum((theta - np.array([1.0, 0.01, 0.0, 0.0])) ** 2 / 1e-4, axis=1)
-
-
-def fitted_on_host():
-    """A PolynomialDecomposition whose chain comes from the host sampler around a NumPy log-probability (as in
-    tests/test_histogram.py): nothing here touches the device."""
-    import bisip_amd
-    from bisip_amd.sampler import EnsembleSampler
-    m = bisip_amd.PolynomialDecomposition(bisip_amd.DataFiles()['SIP-K389175'], poly_deg=2, nwalkers=8)
-    np.random.seed(1)
-    s = EnsembleSampler(8, 4, gaussian_logp)
-    s.run_mcmc(np.array([1.0, 0.01, 0.0, 0.0]) + 1e-3 * np.random.randn(8, 4), 20)
-    m._sampler = s
-    m._Inversion__fitted = True
-    return m
-
-
 @pytest.mark.parametrize('kw', [dict(), dict(discard=5, thin=3)])
 def test_inversion_traces_with_the_host_sampler(kw):
     m = fitted_on_host()
