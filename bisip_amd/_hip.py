@@ -172,6 +172,10 @@ SYMBOLS = {
     'bisip_response_moments_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                                   ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    'bisip_fit_quality_workspace': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    'bisip_fit_quality_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                             ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     'bisip_columns_percentiles_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int,
                                                      ctypes.c_void_p, ctypes.c_void_p]),
     'bisip_ctx_reduced_check': (ctypes.c_int, [ctypes.c_void_p, _dp, ctypes.c_int64, _dp, _dp]),
@@ -681,6 +685,21 @@ class HipContext:
                                                     int(n_samples), int(sample_stride), int(walkers_per_ensemble),
                                                     response_kind(kind), d_mean_ptr or None, d_std_ptr or None,
                                                     d_work_ptr or None, int(work_bytes), ctypes.c_void_p(stream)))
+
+    def fit_quality_workspace(self, n_samples, n_spectra, walkers_per_ensemble):
+        """Bytes of device scratch fit_quality_dev needs (0: none; negative: shape not supported)."""
+        return int(self._lib.bisip_fit_quality_workspace(self._h, int(n_samples), int(n_spectra), int(walkers_per_ensemble)))
+
+    def fit_quality_dev(self, first_spectrum, n_spectra, d_chain_ptr, n_samples, sample_stride, walkers_per_ensemble,
+                        d_mean_q_ptr, d_var_q_ptr, d_lmeh_ptr, d_work_ptr=0, work_bytes=0, stream=0):
+        """Per data point over the used samples of ``n_spectra`` spectra, with ``q = (y - forward)^2 / sigma^2``: the mean
+        of q, its variance (ddof = 1) and ``log(mean(exp(-q / 2)))``: d_mean_q, d_var_q, d_lmeh (n_spectra, 2, N), any
+        0 / None but not all.  ``d_chain_ptr``: walker 0 of ``first_spectrum`` in the first used sample.  Device pointers
+        (ints), asynchronous on ``stream``."""
+        _check(self._lib.bisip_fit_quality_dev(self._h, int(first_spectrum), int(n_spectra), d_chain_ptr or None,
+                                               int(n_samples), int(sample_stride), int(walkers_per_ensemble),
+                                               d_mean_q_ptr or None, d_var_q_ptr or None, d_lmeh_ptr or None,
+                                               d_work_ptr or None, int(work_bytes), ctypes.c_void_p(stream)))
 
     def forward_spectra_dev(self, first_spectrum, n_spectra, d_theta_ptr, W, d_Z_ptr, stream=0):
         """Batch context: forward of W rows over n_spectra consecutive spectra, W / n_spectra rows each

@@ -13,6 +13,7 @@ from . import _hip, decomposition
 from .autocorr import AutocorrError
 from .covariance import BatchCovariance
 from .ess import BatchEss
+from .fitquality import BatchFitQuality
 from .interval import BatchIntervals
 from .dist import shard_range
 from .response import BatchResponse
@@ -50,7 +51,7 @@ def default_params(model, n_modes=1, poly_deg=5):
     return p
 
 
-class SpectraBatch(BatchCovariance, BatchIntervals, BatchEss, BatchResponse):
+class SpectraBatch(BatchCovariance, BatchIntervals, BatchEss, BatchResponse, BatchFitQuality):
     """E spectra inverted together with the same model class.
 
     Args:

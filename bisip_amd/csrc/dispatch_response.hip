@@ -28,39 +28,14 @@
 //     results then in ascending order ((w0 + w1) + w2) + w3.
 //   * Segments are merged in ascending order S = (...((s_0 + s_1) + s_2) ...) by k_response_merge (nseg > 1).
 //   * mean = c + S / R;  var = (P - (S * S) / R) / R, < 0 becomes 0 (a NaN stays);  std = sqrt(var).
-#include "host.h"
+#include "response_plan.h"                    // RM_THREADS, rm_plan, check_response_shape: shared with dispatch_fit.hip
 
 using namespace bisip;
 using namespace bisip::host;
 
 namespace {
 
-constexpr int RM_THREADS = 256;
 constexpr int RM_JT = 8;                      // frequencies per tile: 4 * RM_JT running sums per lane
-constexpr long long RM_WGS = 2048;            // workgroups wanted of few spectra
-constexpr long long RM_SEG_MIN = 1024;        // rows of a segment at least
-constexpr long long RM_ONE_SEGMENT = 256;     // spectra from which a workgroup per spectrum fills the chip
-constexpr long long RM_SEG_MAX = 1LL << 30;   // rows of a segment at most: 32-bit row numbers inside it
-
-struct RmPlan {
-    long long R, seg_rows, nseg;
-};
-
-RmPlan rm_plan(long long n, long long E, long long Wp)
-{
-    RmPlan p{};
-    p.R = n * Wp;
-    if (E >= RM_ONE_SEGMENT) {
-        p.seg_rows = p.R;
-    } else {
-        const long long want = RM_WGS / E;
-        p.seg_rows = (p.R + want - 1) / want;
-        if (p.seg_rows < RM_SEG_MIN) p.seg_rows = RM_SEG_MIN;
-    }
-    if (p.seg_rows > RM_SEG_MAX) p.seg_rows = RM_SEG_MAX;
-    p.nseg = (p.R + p.seg_rows - 1) / p.seg_rows;
-    return p;
-}
 
 struct RmArgs {
     const double *chain;         // walker 0 of the call's first spectrum in the first used sample
@@ -238,15 +213,6 @@ int dispatch_response(const bisip_ctx *c, const RmArgs &a, unsigned blocks, int 
     case BISIP_MODEL_SHIN2015: return launch_response<Shin>(a, blocks, kind, st);
     }
     return fail(BISIP_EUNSUPPORTED, "no response-moments kernel for this model shape");
-}
-
-int check_response_shape(const bisip_ctx *c, int64_t n_samples, int64_t n_spectra, int64_t walkers_per_ensemble)
-{
-    if (!c) return fail(BISIP_EINVAL, "null context");
-    if (n_samples < 1 || n_samples > 0x7fffffffLL || n_spectra < 1 || n_spectra > c->E || walkers_per_ensemble < 1 ||
-        walkers_per_ensemble > 0x7fffffffLL / (2 * BISIP_MAX_NDIM))
-        return fail(BISIP_EINVAL, "bad chain shape");
-    return BISIP_OK;
 }
 
 // bytes of the segments' sums and the shifts; 0 with one segment, -1 when the grid does not exist

@@ -16,6 +16,7 @@ from .chainview import ChainView, _merge_device_parts, device_moments, device_pe
 from .convergence import device_rhat
 from .covariance import corr_from_cov, device_best_sample, device_cov
 from .ess import device_ess, device_mcse_mean
+from .fitquality import device_fit_quality
 from .interval import device_hdi
 from .response import device_model_moments
 from .trace import device_trace
@@ -290,3 +291,11 @@ class DeviceChainSummaries:
         where it lies (bisip_response_moments_dev; ``chain_on_device``), else over an upload of the used samples only.
         No response is stored."""
         return device_model_moments(self.used_samples_dev(discard, thin), self.backend.ctx, kind)
+
+    def fit_quality(self, discard=0, thin=1):
+        """``(mean_q, var_q, lmeh)`` per data point of every ensemble's spectrum, ``(n_ensembles, 2, N)`` each, over the
+        used samples: with ``q = (zn - forward(get_chain(discard, thin, flat=True)))**2 / zn_err**2`` the mean of ``q``,
+        its variance (ddof = 1) and ``log(mean(exp(-q / 2)))`` (bisip_amd.fitquality.fit_sums), evaluated and summed in
+        one pass over the chain where it lies (bisip_fit_quality_dev; ``chain_on_device``), else over an upload of the
+        used samples only.  No response is stored."""
+        return device_fit_quality(self.used_samples_dev(discard, thin), self.backend.ctx)

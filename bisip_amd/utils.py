@@ -15,6 +15,7 @@ import numpy as np
 from .chainview import used_range
 from .covariance import ModelCovariance
 from .ess import ModelEss
+from .fitquality import ModelFitQuality
 from .interval import ModelIntervals
 from .response import ModelResponse
 
@@ -183,11 +184,12 @@ def refuse_discard_of_a_chain(kwargs):
                          'thin keywords to parse the full chain. Do not pass both.')
 
 
-class utils(ModelCovariance, ModelIntervals, ModelEss, ModelResponse):
+class utils(ModelCovariance, ModelIntervals, ModelEss, ModelResponse, ModelFitQuality):
     """Mixin with the reference's utility methods (src/bisip/utils.py:15); the posterior covariance, correlation and best
     sample come from bisip_amd.covariance.ModelCovariance, the highest-density intervals from
     bisip_amd.interval.ModelIntervals, the effective sample sizes from bisip_amd.ess.ModelEss, the amplitude / phase
-    bands and the moments of the model response from bisip_amd.response.ModelResponse."""
+    bands and the moments of the model response from bisip_amd.response.ModelResponse, WAIC, DIC and the per-point misfit
+    from bisip_amd.fitquality.ModelFitQuality."""
 
     def load_data(self, filename, headers=1, ph_units='mrad'):
         return load_data(filename, headers, ph_units)

@@ -46,7 +46,8 @@ extern "C" {
  * 6: rtd_integrals_dev, rtd_columns_dev (additions only); chain_range_dev, chain_histograms_dev,
  *    chain_pair_histograms_dev, then chain_trace_dev (+ _workspace, _lds_walkers), then chain_rhat_dev (+ _workspace),
  *    then chain_cov_dev and chain_best_sample_dev (+ _workspace), then forward_columns_kind_dev,
- *    forward_percentiles_kind and response_moments_dev (+ _workspace) with BISIP_RESPONSE_RI / _PA
+ *    forward_percentiles_kind and response_moments_dev (+ _workspace) with BISIP_RESPONSE_RI / _PA, then
+ *    fit_quality_dev (+ _workspace)
  *    came later under the same number (additions only: a caller that needs them looks the symbols up). */
 #define BISIP_ABI_VERSION 6
 
@@ -667,6 +668,35 @@ int64_t bisip_response_moments_workspace(bisip_ctx *ctx, int64_t n_samples, int6
 int bisip_response_moments_dev(bisip_ctx *ctx, int64_t first_spectrum, int64_t n_spectra, const double *d_chain,
                                int64_t n_samples, int64_t sample_stride, int64_t walkers_per_ensemble, int kind,
                                double *d_mean, double *d_std, void *d_work, int64_t work_bytes, void *stream);
+
+/* FIT QUALITY per data point (Re and Im at each frequency) over the used samples of a chain resident in device memory:
+ * with q = (y - Z)^2 * iv of a row -- y the normalised measurement, Z = forward(row), iv the context's inverse variance
+ * (the record's rec[0..3]); d = y - Z, t = d * d, q = t * iv, each rounded on its own --
+ *   d_mean_q = mean of q over the R rows (near 1: the point is fitted to its error bar),
+ *   d_var_q  = variance of q with ddof = 1 (R = 1: NaN),
+ *   d_lmeh   = log(mean(exp(-q / 2))), evaluated as -m / 2 + log(mean(exp(-(q - m) / 2))), m = min q,
+ * (n_spectra, 2, N) each; any may be NULL, not all three.  WAIC and the per-point misfit are made of these
+ * (bisip_amd/fitquality.py holds the definitions: pointwise_q, fit_sums, waic).  Chain layout, d_chain, first_spectrum,
+ * argument checks and error codes: those of bisip_response_moments_dev; fused in the same way, nothing but the outputs is
+ * written.  A row with a parameter that is not finite counts as q = NaN: it makes the three outputs of ITS spectrum NaN
+ * at every point and no other spectrum's.
+ * Order.  Segments and row slots are those of bisip_response_moments_dev (the same plan; a slot takes its rows in
+ * ascending order; slots pairwise within each run of 64, 32, 16, ..., 1 apart, the four runs then in ascending order;
+ * segments in ascending order).  mean_q, var_q: shifted sums, c = q of walker 0 of the spectrum's first used sample,
+ * d = q - c, S = sum d, P = sum d * d (the product rounded on its own), mean_q = c + S / R, var_q = (P - (S * S) / R) /
+ * (R - 1) with < 0 -> 0 (a NaN stays).  lmeh: every slot keeps (m, s), empty (+inf, 0); a row q >= m gives s = s +
+ * exp(-(q - m) / 2), a row q < m gives s = s * exp(-(m - q) / 2) + 1, m = q (one exp per row, nothing fused); two pairs
+ * merge to m' = min(m_a, m_b), the side with the larger m scaled by exp(-(m - m') / 2), the other (both, when equal)
+ * not, s' = s_a + s_b, along the same tree as the sums; lmeh = -m / 2 + log(s / R).  exp and log are the device
+ * library's.  (The frequencies go in tiles of 4, each a pass over the segment's rows: 32 doubles of state per lane; the
+ * tiling changes no output.)  d_work: bisip_fit_quality_workspace() BYTES (0: none needed, one segment; < 0: shape not
+ * supported) for the segments' states and the shifts, 8-byte aligned.  No floating-point atomics: the same bits on every
+ * call (fitquality.ordered_fit_sums gives those of mean_q and var_q in NumPy from the same responses, and lmeh in the
+ * same order with NumPy's exp).  64-bit offsets.  Asynchronous on stream, no host synchronisation. */
+int64_t bisip_fit_quality_workspace(bisip_ctx *ctx, int64_t n_samples, int64_t n_spectra, int64_t walkers_per_ensemble);
+int bisip_fit_quality_dev(bisip_ctx *ctx, int64_t first_spectrum, int64_t n_spectra, const double *d_chain,
+                          int64_t n_samples, int64_t sample_stride, int64_t walkers_per_ensemble, double *d_mean_q,
+                          double *d_var_q, double *d_lmeh, void *d_work, int64_t work_bytes, void *stream);
 
 /* Host: the stretch move's random stream in numpy.random.RandomState order for n_steps
  * iterations of a W-walker ensemble (the contract is bisip_amd/sampler.py:draw_step).
