@@ -210,6 +210,11 @@ SYMBOLS = {
                                                   ctypes.c_void_p, ctypes.c_void_p]),
     'bisip_polydecomp_reduced_reference': (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, ctypes.POINTER(ModelDesc),
                                                           _dp, ctypes.c_int64, _dp]),
+    'bisip_reduced_emulate': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _dp, ctypes.POINTER(ctypes.c_float), _dp, _dp, _dp,
+                                             ctypes.c_double, ctypes.c_double, _dp, _dp, _dp, ctypes.c_int64, _dp]),
+    'bisip_ctx_reduced_operands': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, _dp,
+                                                  ctypes.POINTER(ctypes.c_float), _dp, _dp, _dp, _dp, _dp,
+                                                  ctypes.POINTER(ctypes.c_int)]),
     'bisip_abi_version': (ctypes.c_int, []),
     'bisip_device_count': (ctypes.c_int, []),
     'bisip_last_error': (ctypes.c_char_p, []),
@@ -350,6 +355,33 @@ def polydecomp_reduced_reference(w, zn, zn_err, taus, log_taus, c_exp, theta):
     return out
 
 
+def reduced_emulate(ops, bounds, theta):
+    """Host-only, no GPU: what the QR-reduced kernels store for the rows of ``theta``, bit for bit
+    (bisip_reduced_emulate: the host emulation of their arithmetic, then the open-box prior).  ``ops``: the operands
+    as a kernel holds them -- ``comp`` (bool), ``R`` the packed upper triangle (row-major), ``Rlo`` (float32, compensated
+    only), ``bhat``, ``e``, ``elo`` (compensated only), ``rest``, ``lconst`` -- e.g. what ``HipContext.reduced_operands``
+    returns; ``bounds`` (2, n)."""
+    comp = bool(ops['comp'])
+    bhat = _c(ops['bhat']).ravel()
+    n = bhat.size
+    R, e = _c(ops['R']).ravel(), _c(ops['e']).ravel()
+    Rlo = None if ops.get('Rlo') is None else np.ascontiguousarray(ops['Rlo'], dtype=np.float32).ravel()
+    elo = None if ops.get('elo') is None else _c(ops['elo']).ravel()
+    tri = n * (n + 1) // 2
+    if R.size != tri or e.size != n or (Rlo is not None and Rlo.size != tri) or (elo is not None and elo.size != n):
+        raise ValueError(f'operands of n = {n}: R and Rlo hold {tri} entries, bhat, e and elo {n}')
+    b = _c(bounds).reshape(2, -1)
+    lo, hi = _c(b[0]), _c(b[1])
+    if lo.size != n:
+        raise ValueError(f'bounds must have shape (2, {n})')
+    theta = _c(theta).reshape(-1, n)
+    out = np.empty(theta.shape[0])
+    _check(load_library().bisip_reduced_emulate(n, int(comp), _p(R), None if Rlo is None else Rlo.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                                _p(bhat), _p(e), None if elo is None else _p(elo), float(ops['rest']),
+                                                float(ops['lconst']), _p(lo), _p(hi), _p(theta), theta.shape[0], _p(out)))
+    return out
+
+
 def device_count():
     return int(load_library().bisip_device_count())
 
@@ -458,6 +490,22 @@ class HipContext:
         a, b = ctypes.c_int64(0), ctypes.c_int64(0)
         _check(self._lib.bisip_ctx_reduced_tiers(self._h, ctypes.byref(a), ctypes.byref(b)))
         return int(a.value), int(b.value)
+
+    def reduced_operands(self, spectrum=0, tier=0):
+        """PolynomialDecomposition: the host copies of what the device holds for ``spectrum`` on QR-reduced tier
+        ``tier`` (0 plain, 1 compensated) under the current prior box (bisip_ctx_reduced_operands; launches and
+        estimates nothing), as ``reduced_emulate`` takes them, plus ``runs``: does the present variant send this
+        spectrum through this tier?  ValueError for a tier that holds no operands of that spectrum."""
+        n = self.poly_deg + 2
+        tri = n * (n + 1) // 2
+        R, Rlo = np.empty(tri), np.zeros(tri, dtype=np.float32)
+        bhat, e, elo, rest, lconst = np.empty(n), np.empty(n), np.empty(n), np.empty(1), np.empty(1)
+        runs = ctypes.c_int(0)
+        _check(self._lib.bisip_ctx_reduced_operands(self._h, int(spectrum), int(tier), _p(R),
+                                                    Rlo.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), _p(bhat), _p(e), _p(elo),
+                                                    _p(rest), _p(lconst), ctypes.byref(runs)))
+        return dict(comp=int(tier) == 1, R=R, Rlo=Rlo if int(tier) == 1 else None, bhat=bhat, e=e, elo=elo,
+                    rest=float(rest[0]), lconst=float(lconst[0]), runs=bool(runs.value))
 
     @property
     def loop_flags(self):

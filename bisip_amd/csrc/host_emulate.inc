@@ -3,6 +3,10 @@
 // one instruction instead of a libm call (a context's estimate is ~100,000 of them); the caller picks at run
 // time with __builtin_cpu_supports("fma").  Both are correctly rounded fused multiply-adds: the same bits.
 // EMU(name) names the instantiation, EMU_ATTR carries the target attribute.
+// What holds chi2_kernel and the kernels together: tests/test_reduced_emulation.py compares it (through
+// bisip_reduced_emulate) with an exact rational statement of the sequence, tests/test_gpu_reduced_bits.py compares
+// every instantiation and launch route of logprob_row_reduced with it -- both by equality of bits.  Change one side
+// and the other has to follow.
 
 // logprob_row_reduced<P, COMP> (kernels.h) in the same double arithmetic, operation for operation.
 // R: (n,n) the triangle the kernel holds; Rlo: its low word as the kernel holds it (floats; compensated form only)

@@ -530,6 +530,14 @@ int candidates(int n, const std::vector<ld> &bhat_ls, const double *lo, const do
 
 }  // namespace
 
+// chi2_kernel of host_emulate.inc for callers outside this file (bisip_reduced_emulate), picked as worst_error picks it
+double reduced_chi2_kernel(int n, const double *R, const float *Rlo, const double *bhat, const double *e, const double *elo,
+                           double rest, const double *th, bool comp)
+{
+    return have_fma() ? chi2_kernel_fma(n, R, Rlo, bhat, e, elo, rest, th, comp)
+                      : chi2_kernel_base(n, R, Rlo, bhat, e, elo, rest, th, comp);
+}
+
 // BISIP_SHELL_WEIGHT (a test hook: tests force an estimate to pass with 0) changes which reduced tier AUTO
 // selects, so an override is never silent: it is validated ([0, 1], else ignored) and announced on stderr once
 // per process.  Read on every (re)estimate; BISIP_HOST_SCALAR_ESTIMATE (have_avx2) is latched on first use.

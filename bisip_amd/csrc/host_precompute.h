@@ -112,6 +112,10 @@ double reduced_center_plain(const ReducedProblem &p, const ReducedProbes &probes
                             double shell_weight, double *out_bhat, double *out_e, double *out_elo);
 double reduced_center_comp(const ReducedProblem &p, const ReducedProbes &probes, const double *lo, const double *hi,
                            double shell_weight, double *out_bhat, double *out_e, double *out_elo);
+// The emulation itself, for one row: chi^2 as logprob_row_reduced<P, COMP> forms it (host_emulate.inc: chi2_kernel,
+// the instantiation worst_error runs).  R, Rlo: (n,n) row-major, zeros below the diagonal; Rlo and elo: comp only.
+double reduced_chi2_kernel(int n, const double *R, const float *Rlo, const double *bhat, const double *e, const double *elo,
+                           double rest, const double *th, bool comp);
 // Weight of the shell probes: BISIP_SHELL_WEIGHT (a test hook: 0 reproduces an estimate that never looks at
 // the shell) or 0.05.  Read by the caller ONCE per (re)estimation, on its own thread.
 double reduced_shell_weight();

@@ -47,7 +47,7 @@ extern "C" {
  *    chain_pair_histograms_dev, then chain_trace_dev (+ _workspace, _lds_walkers), then chain_rhat_dev (+ _workspace),
  *    then chain_cov_dev and chain_best_sample_dev (+ _workspace), then forward_columns_kind_dev,
  *    forward_percentiles_kind and response_moments_dev (+ _workspace) with BISIP_RESPONSE_RI / _PA, then
- *    fit_quality_dev (+ _workspace)
+ *    fit_quality_dev (+ _workspace), then reduced_emulate and ctx_reduced_operands
  *    came later under the same number (additions only: a caller that needs them looks the symbols up). */
 #define BISIP_ABI_VERSION 6
 
@@ -877,6 +877,28 @@ int bisip_fp64_stream_probe_dev(double *d_out, int rounds, int64_t *wave_instruc
  * bisip_logprob's guard and the estimate behind BISIP_VARIANT_AUTO measure against.  Needs 2N >= poly_deg+2. */
 int bisip_polydecomp_reduced_reference(int N, const double *w, const double *zn, const double *zn_err,
                                        const bisip_model_desc *desc, const double *theta, int64_t W, double *logp);
+
+/* Host-only, no context, no GPU: what the QR-reduced kernels STORE for W rows of theta (W, n), bit for bit -- the
+ * host emulation of their double arithmetic that the estimates behind BISIP_VARIANT_AUTO are measured on
+ * (operation for operation; an fma is one rounding).  n = poly_deg + 2 (2 ... BISIP_MAX_POLY_DEG + 2); comp = 0:
+ * the plain tier, 1: the compensated one.  Operands as a kernel holds them: R the packed upper triangle, row-major,
+ * n (n + 1) / 2 doubles; Rlo its low word, as many floats (comp = 1 only; may be NULL otherwise, like elo);
+ * bhat, e, elo (n,); rest; lconst; the prior box lo, hi (n,).  out[i] = -inf for a row outside the OPEN box (a NaN
+ * or an on-bound value is outside), else fma(-0.5, chi^2, lconst) -- inf and NaN where the kernel's own sums
+ * overflow.  tests/test_gpu_reduced_bits.py holds every instantiation and launch route of the kernels to it. */
+int bisip_reduced_emulate(int n, int comp, const double *R, const float *Rlo, const double *bhat, const double *e,
+                          const double *elo, double rest, double lconst, const double *lo, const double *hi,
+                          const double *theta, int64_t W, double *out);
+
+/* Host-only (reads the context, launches nothing, estimates nothing): the host copies of the operands the device
+ * holds for spectrum `spectrum` of a PolynomialDecomposition context on QR-reduced tier `tier` (0 plain, 1
+ * compensated) under the current prior box, in the layout bisip_reduced_emulate takes: R, Rlo (tier 1; may be NULL
+ * for tier 0), bhat, e, elo, *rest and *lconst (the spectrum's own).  *runs = 1 when the context's present
+ * effective variant sends this spectrum through this tier (a batch on BISIP_VARIANT_AUTO decides per spectrum),
+ * else 0.  BISIP_EINVAL for another model, a bad index or tier, and a tier whose operands do not exist for that
+ * spectrum under the current box (never asked for by a variant, or a batch spectrum that runs the other tier). */
+int bisip_ctx_reduced_operands(const bisip_ctx *ctx, int64_t spectrum, int tier, double *R, float *Rlo, double *bhat,
+                               double *e, double *elo, double *rest, double *lconst, int *runs);
 
 int bisip_abi_version(void);
 int bisip_device_count(void);

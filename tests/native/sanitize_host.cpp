@@ -192,6 +192,9 @@ static void reduced(int N, int S, int D)
         EXPECT(comp >= 0.0 || comp != comp);
         const double q_ref = bisip::reduced_logp_reference(p, th.data());
         EXPECT(std::isfinite(q_ref) && std::fabs(q_ref - ld_ref) <= 1e-6 * (1.0 + std::fabs(ld_ref)));
+        // the kernel emulation behind bisip_reduced_emulate, one row on each tier (e, el: the compensated centre's)
+        EXPECT(std::isfinite(bisip::reduced_chi2_kernel(n, p.Rc.data(), p.Rc_lo.data(), bh.data(), e.data(), el.data(), p.rest_c, th.data(), true)));
+        EXPECT(std::isfinite(bisip::reduced_chi2_kernel(n, p.R.data(), nullptr, bh.data(), e.data(), nullptr, p.rest, th.data(), false)));
     }
 }
 
