@@ -178,6 +178,12 @@ SYMBOLS = {
                                              ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     'bisip_columns_percentiles_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int,
                                                      ctypes.c_void_p, ctypes.c_void_p]),
+    'bisip_q_columns_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                           ctypes.c_void_p]),
+    'bisip_loo_columns_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    'bisip_loo_columns_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int64, ctypes.c_void_p]),
     'bisip_ctx_reduced_check': (ctypes.c_int, [ctypes.c_void_p, _dp, ctypes.c_int64, _dp, _dp]),
     'bisip_read_tables': (ctypes.c_int, [ctypes.POINTER(ctypes.c_char_p), ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
@@ -749,6 +755,13 @@ class HipContext:
                                                d_mean_q_ptr or None, d_var_q_ptr or None, d_lmeh_ptr or None,
                                                d_work_ptr or None, int(work_bytes), ctypes.c_void_p(stream)))
 
+    def q_columns_dev(self, first_spectrum, n_spectra, d_cols_ptr, rows_per_spectrum, stream=0):
+        """The Re / Im columns ``(n_spectra, 2N, rows_per_spectrum)`` that forward_columns_dev wrote become, in place, the
+        squared standardised residuals ``q = (y - Z)^2 * iv`` of their data points (the bits of fitquality.pointwise_q).
+        Device pointer (int), asynchronous on ``stream``."""
+        _check(self._lib.bisip_q_columns_dev(self._h, int(first_spectrum), int(n_spectra), d_cols_ptr or None,
+                                             int(rows_per_spectrum), ctypes.c_void_p(stream)))
+
     def forward_spectra_dev(self, first_spectrum, n_spectra, d_theta_ptr, W, d_Z_ptr, stream=0):
         """Batch context: forward of W rows over n_spectra consecutive spectra, W / n_spectra rows each
         (a multiple of 64 when n_spectra > 1), one launch (device pointers)."""
@@ -1112,6 +1125,21 @@ def columns_percentiles_dev(d_cols_ptr, n_columns, n, percentiles, d_out_ptr, st
     pointers (ints); no workspace."""
     p = _c(percentiles).ravel()
     _check(load_library().bisip_columns_percentiles_dev(d_cols_ptr, int(n_columns), int(n), _p(p), p.size, d_out_ptr, stream))
+
+
+def loo_columns_workspace(n, columns, tail_len):
+    """BYTES of device workspace for loo_columns_dev (negative: shape refused)."""
+    return int(load_library().bisip_loo_columns_workspace(int(n), int(columns), int(tail_len)))
+
+
+def loo_columns_dev(d_q_ptr, n, columns, tail_len, d_elpd_rel_ptr, d_khat_ptr, d_sigma_ptr, d_ntail_ptr, d_work_ptr,
+                    work_bytes, stream=0):
+    """PSIS-LOO of ``columns`` contiguous device columns of ``n`` values ``q`` (bisip_amd.loo.psis_loo_columns): d_elpd_rel,
+    d_khat, d_sigma (float64) and d_ntail (int64), ``(columns,)`` each, any 0 / None but not all.  Device pointers (ints),
+    asynchronous on ``stream``."""
+    _check(load_library().bisip_loo_columns_dev(d_q_ptr or None, int(n), int(columns), int(tail_len), d_elpd_rel_ptr or None,
+                                                d_khat_ptr or None, d_sigma_ptr or None, d_ntail_ptr or None,
+                                                d_work_ptr or None, int(work_bytes), stream))
 
 
 def grouped_percentiles_workspace(n_groups, n_rows, n_cols, n_percentiles):

@@ -16,6 +16,7 @@ from .ess import BatchEss
 from .fitquality import BatchFitQuality
 from .interval import BatchIntervals
 from .dist import shard_range
+from .loo import BatchLoo
 from .response import BatchResponse
 from .sampler import DeviceEnsembleSampler
 from .summaries import device_model_percentiles
@@ -51,7 +52,7 @@ def default_params(model, n_modes=1, poly_deg=5):
     return p
 
 
-class SpectraBatch(BatchCovariance, BatchIntervals, BatchEss, BatchResponse, BatchFitQuality):
+class SpectraBatch(BatchCovariance, BatchIntervals, BatchEss, BatchResponse, BatchFitQuality, BatchLoo):
     """E spectra inverted together with the same model class.
 
     Args:

@@ -19,7 +19,7 @@ everything: the mean of ``q`` (the misfit: near 1, the point is fitted to its er
   models (bisip_amd.utils.utils) and of SpectraBatch, as mixins.
 
 The rows of a spectrum are numbered ``k * Wp + w`` (sample ``k``, walker ``w``): the order of ``get_chain(flat=True)``.
-PSIS-LOO needs a sort per data point and is not here.
+PSIS-LOO, which needs a sort per data point, is bisip_amd.loo.
 """
 
 import warnings
@@ -276,9 +276,10 @@ class ModelFitQuality:
     def get_waic(self, chain=None, **kwargs):
         """The widely applicable information criterion of the fit (bisip_amd.fitquality.waic): a dict of ``elpd_waic``,
         ``p_waic``, ``waic = -2 elpd_waic``, its standard error ``se``, ``n_high`` (points with ``p_waic_i > 0.4``: WAIC is
-        then unreliable) and the pointwise ``lppd``, ``p_waic_i``, ``elpd_i``, ``(2, N)`` each.  The sums over the chain
-        are taken on the device; ``compare_waic`` ranks the results of several models of one spectrum.  ``chain`` /
-        ``discard`` / ``thin`` as get_model_percentile."""
+        then unreliable; ``get_loo`` is the estimate to turn to, and its ``pareto_k`` shows which points) and the pointwise
+        ``lppd``, ``p_waic_i``, ``elpd_i``, ``(2, N)`` each.  The sums over the chain are taken on the device;
+        ``compare_waic`` ranks the results of several models of one spectrum.  ``chain`` / ``discard`` / ``thin`` as
+        get_model_percentile."""
         _, var_q, lmeh = self._fit_sums(chain, kwargs)
         return waic_from_sums(var_q, lmeh, np.log(self._data['zn_err'] ** 2))
 

@@ -17,6 +17,7 @@ from .covariance import ModelCovariance
 from .ess import ModelEss
 from .fitquality import ModelFitQuality
 from .interval import ModelIntervals
+from .loo import ModelLoo
 from .response import ModelResponse
 
 _COLUMNS = ('freq', 'amp', 'pha', 'amp_err', 'pha_err')
@@ -184,12 +185,12 @@ def refuse_discard_of_a_chain(kwargs):
                          'thin keywords to parse the full chain. Do not pass both.')
 
 
-class utils(ModelCovariance, ModelIntervals, ModelEss, ModelResponse, ModelFitQuality):
+class utils(ModelCovariance, ModelIntervals, ModelEss, ModelResponse, ModelFitQuality, ModelLoo):
     """Mixin with the reference's utility methods (src/bisip/utils.py:15); the posterior covariance, correlation and best
     sample come from bisip_amd.covariance.ModelCovariance, the highest-density intervals from
     bisip_amd.interval.ModelIntervals, the effective sample sizes from bisip_amd.ess.ModelEss, the amplitude / phase
     bands and the moments of the model response from bisip_amd.response.ModelResponse, WAIC, DIC and the per-point misfit
-    from bisip_amd.fitquality.ModelFitQuality."""
+    from bisip_amd.fitquality.ModelFitQuality, PSIS-LOO and the Pareto k of every point from bisip_amd.loo.ModelLoo."""
 
     def load_data(self, filename, headers=1, ph_units='mrad'):
         return load_data(filename, headers, ph_units)

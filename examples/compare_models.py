@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Which model does the spectrum support: Pelton Cole-Cole with one mode and with two, fitted to the same spectrum and
-ranked by WAIC, and where the better one still misses the data.  The chains stay on the GPU; the sums over them are taken
-there (bisip_fit_quality_dev)."""
+ranked by WAIC and by PSIS-LOO, and where the better one still misses the data.  The chains stay on the GPU; the sums over
+them (bisip_fit_quality_dev) and the Pareto-smoothed tails of every data point (bisip_loo_columns_dev) are taken there."""
 import os
 import sys
 
@@ -11,9 +11,10 @@ import numpy as np
 
 from bisip_amd import DataFiles, PeltonColeCole
 from bisip_amd.fitquality import compare_waic
+from bisip_amd.loo import compare_loo
 
 filepath = DataFiles()['SIP-K389174']                         # two bumps in its imaginary part (docs/tutorials/pelton.ipynb)
-results, models = {}, {}
+results, loos, models = {}, {}, {}
 for n_modes in (1, 2):
     np.random.seed(42)
     model = PeltonColeCole(filepath, nwalkers=64, nsteps=2000, n_modes=n_modes)
@@ -21,7 +22,7 @@ for n_modes in (1, 2):
         model.params.update(log_tau1=[-5, 5], log_tau2=[-15, -10])
     model.fit(chain='device')
     name = f'{n_modes} mode' + 's' * (n_modes > 1)
-    results[name], models[name] = model.get_waic(discard=1000), model
+    results[name], loos[name], models[name] = model.get_waic(discard=1000), model.get_loo(discard=1000), model
     dic = model.get_dic(discard=1000)
     print(f'{name}: DIC {dic["dic"]:.1f}, p_D {dic["p_d"]:.1f}; {results[name]["n_high"]} points with p_waic > 0.4')
 
@@ -29,7 +30,15 @@ print('model      elpd_waic  p_waic   d_elpd    d_se')
 for row in compare_waic(results):                             # the best model first
     print(f'{row["name"]:<10} {row["elpd_waic"]:9.1f} {row["p_waic"]:7.1f} {row["d_elpd"]:8.1f} {row["d_se"]:7.1f}')
 
+# where n_high > 0 WAIC is unreliable: PSIS-LOO is the estimate to turn to, and pareto_k shows which points make it fragile
+print('model       elpd_loo   p_loo   d_elpd    d_se  n_bad')
+for row in compare_loo(loos):
+    print(f'{row["name"]:<10} {row["elpd_loo"]:9.1f} {row["p_loo"]:7.1f} {row["d_elpd"]:8.1f} {row["d_se"]:7.1f} {row["n_bad"]:6d}')
+
 best = compare_waic(results)[0]['name']
 misfit = models[best].get_pointwise_misfit(discard=1000)      # (2, N): near 1, the point is fitted to its error bar
 worst = np.unravel_index(np.argmax(misfit), misfit.shape)
 print(f'{best}: misfit at most {misfit.max():.1f}, at the {("real", "imaginary")[worst[0]]} part of frequency {worst[1]}')
+k = loos[best]['pareto_k']
+print(f'{best}: Pareto k at most {k.max():.2f} (threshold {loos[best]["k_threshold"]:.2f}), at the '
+      f'{("real", "imaginary")[np.unravel_index(np.argmax(k), k.shape)[0]]} part of frequency {np.unravel_index(np.argmax(k), k.shape)[1]}')

@@ -47,7 +47,8 @@ extern "C" {
  *    chain_pair_histograms_dev, then chain_trace_dev (+ _workspace, _lds_walkers), then chain_rhat_dev (+ _workspace),
  *    then chain_cov_dev and chain_best_sample_dev (+ _workspace), then forward_columns_kind_dev,
  *    forward_percentiles_kind and response_moments_dev (+ _workspace) with BISIP_RESPONSE_RI / _PA, then
- *    fit_quality_dev (+ _workspace), then reduced_emulate and ctx_reduced_operands
+ *    fit_quality_dev (+ _workspace), then reduced_emulate and ctx_reduced_operands, then q_columns_dev and
+ *    loo_columns_dev (+ _workspace)
  *    came later under the same number (additions only: a caller that needs them looks the symbols up). */
 #define BISIP_ABI_VERSION 6
 
@@ -697,6 +698,42 @@ int64_t bisip_fit_quality_workspace(bisip_ctx *ctx, int64_t n_samples, int64_t n
 int bisip_fit_quality_dev(bisip_ctx *ctx, int64_t first_spectrum, int64_t n_spectra, const double *d_chain,
                           int64_t n_samples, int64_t sample_stride, int64_t walkers_per_ensemble, double *d_mean_q,
                           double *d_var_q, double *d_lmeh, void *d_work, int64_t work_bytes, void *stream);
+
+/* PSIS-LOO, step 1: the Re / Im columns that bisip_forward_columns_dev wrote for n_spectra consecutive spectra starting
+ * with first_spectrum -- d_cols (n_spectra, 2N, rows_per_spectrum) -- become, where they lie, the squared standardised
+ * residuals q = (y - Z)^2 * iv of their data point: y and iv from the frequency's record as for bisip_fit_quality_dev,
+ * d = y - Z, t = d * d, q = t * iv, each rounded on its own (the bits of fitquality.pointwise_q).  Nothing is summed.
+ * 64-bit offsets; asynchronous on stream. */
+int bisip_q_columns_dev(bisip_ctx *ctx, int64_t first_spectrum, int64_t n_spectra, double *d_cols, int64_t rows_per_spectrum,
+                        void *stream);
+
+/* PSIS-LOO, step 2 (Vehtari, Simpson, Gelman, Yao & Gabry; bisip_amd/loo.py holds the definition: psis_loo_columns), no
+ * context: d_q (columns, n) contiguous columns of n >= 2 values q, the log importance ratio of a value being q / 2.  Per
+ * column, with s = sort(q), qmax = s[n - 1], u = s[n - tail_len - 1], r(x) = exp((x - qmax) / 2), eu = r(u): the tail is
+ * the values > u, n_tail <= tail_len of them (ties at u stay in the body).  n_tail <= 4: khat = +inf, sigma = NaN, weights
+ * w = r.  Else the generalised Pareto distribution is fitted to x = r(tail) - eu in ascending order (Zhang & Stephens with
+ * the weakly informative prior: m = 30 + floor(sqrt(n_tail)) profile points b_j, k_j = mean(log1p(-b_j x)), L_j = n_tail
+ * ((log(-b_j / k_j) - k_j) - 1), w_j = 1 / sum_i exp(L_i - L_j), b = sum b_j w_j, k = mean(log1p(-b x)), sigma = -k / b,
+ * khat = k n_tail / (n_tail + 10) + 5 / (n_tail + 10); a khat that is not finite becomes +inf, sigma NaN and w = r) and the
+ * tail's weights are w_i = min(eu + (sigma expm1(-khat log1p(-p_i))) / khat, 1), p_i = (i + 0.5) / n_tail.
+ *   d_elpd_rel = (-qmax / 2 + log((n - n_tail) + sum_tail w / r)) - log(sum_body r + sum_tail w)   (unsmoothed: w / r is 1),
+ *   d_khat, d_sigma, d_ntail (int64): (columns,) each; any may be NULL, not all four.
+ * A column that holds a NaN gives NaN elpd_rel, khat and sigma and n_tail = 0, and touches no other column.
+ * Order.  u and qmax are order statistics (the selection of bisip_columns_percentiles_dev, raw).  Body sum: the column in
+ * chunks of 4096 values; value i of a chunk goes to slot i mod 256, a slot adds r of its values <= u in ascending order from
+ * 0.0 (a value of the tail adds 0.0); slots pairwise within each run of 64, 32, 16, ..., 1 apart, the four runs then in
+ * ascending order; chunks in ascending order.  The tail is sorted (one segmented sort of columns * tail_len values, open
+ * slots padded with u).  Profile point j: x_i to slot i mod 64 in ascending order, slots pairwise 32 ... 1 apart.  The
+ * softmax denominators and b: ascending.  k, sum w and sum w / r: element i to slot i mod 256 in ascending order, then the
+ * tree of the body sum.  exp, log, log1p, expm1 are the device library's; nothing is fused.  No floating-point atomics
+ * (integer atomics reserve the tail's slots; the sort removes their order): the same bits on every call
+ * (loo.ordered_columns restates the order with NumPy's functions).  64-bit offsets.
+ * d_work: bisip_loo_columns_workspace() BYTES (< 0: shape refused).  BISIP_EINVAL: null, n < 2, tail_len outside [1, n - 1],
+ * short workspace; BISIP_EUNSUPPORTED: columns * tail_len > 2^31 - 1 (one sort), tail_len > 51,528 (256 profile points).
+ * Asynchronous on stream, no host synchronisation. */
+int64_t bisip_loo_columns_workspace(int64_t n, int64_t columns, int64_t tail_len);
+int bisip_loo_columns_dev(const double *d_q, int64_t n, int64_t columns, int64_t tail_len, double *d_elpd_rel, double *d_khat,
+                          double *d_sigma, int64_t *d_ntail, void *d_work, int64_t work_bytes, void *stream);
 
 /* Host: the stretch move's random stream in numpy.random.RandomState order for n_steps
  * iterations of a W-walker ensemble (the contract is bisip_amd/sampler.py:draw_step).
