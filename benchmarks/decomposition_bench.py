@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""PolynomialDecomposition's integrating parameters and RTD bands of device-resident chains
-(bisip_rtd_integrals_dev, bisip_rtd_columns_dev + the chain summaries).
+"""PolynomialDecomposition's integrating parameters, RTD bands and relaxation descriptors of device-resident chains
+(bisip_rtd_integrals_dev, bisip_rtd_columns_dev, bisip_rtd_descriptors_dev + the chain summaries).
 
 Three shapes: the cfg5 slice (512 spectra x 256 walkers, P = 5, 1000 stored, discard 500), one ensemble of
 32 walkers x 5000 samples, and one ensemble of 131,072 walkers x 200 samples.  The chains are rows drawn
@@ -9,6 +9,10 @@ uniformly from the prior box on the device; log_tau is the 64-point grid of a 32
     the public get_integrating_mean, get_integrating_std and get_integrating_percentile make them (each call
     builds the derived chain again: three integrals launches, two moment passes, one percentile selection), and
     get_rtd_percentile;
+  * descriptors_ms, integrals_ms, columns_ms: the three C entry points alone on the same chain -- the relaxation
+    descriptors (peak, tau_10, tau_50, tau_90), the integrating parameters, and every m_l in passes under
+    decomposition.RTD_PASS_BYTES (no percentile taken) -- medians of 5 with the calls alternating, and the descriptors'
+    time as a ratio to the other two;
   * kernel_ms: the library's kernels per call from a separate `rocprofv3 --kernel-trace --stats` run;
   * the integrals kernel's chain bytes over its kernel time, as a fraction of the 8 TB/s HBM peak, and the columns
     kernel's write rate beside the recorded rate of the forward columns kernel (5.3 TB/s, README);
@@ -75,6 +79,54 @@ def device_calls(x, E, Wp, P, n, discard):
     return integrating, band
 
 
+def entry_points(x, E, Wp, P, n, discard):
+    """The three C entry points alone on the used samples: (descriptors, integrals, columns), outputs allocated once."""
+    import torch
+    from bisip_amd import _hip
+    from bisip_amd import decomposition as dc
+    from bisip_amd.chainview import ChainView
+    W, ndim, L = E * Wp, P + 2, LOG_TAU.size
+    v = ChainView(x, n, E, Wp, ndim, offset=discard * W * ndim, stride=W * ndim)
+    q = np.asarray(dc.DEFAULT_FRACTIONS)
+    d_lt, d_q = v.upload(LOG_TAU), v.upload(q)
+    d_S, d_nf = v.upload(dc.power_sums(LOG_TAU, ndim)), v.upload(norm_factors(E))
+    G = int(min(E, max(1, dc.RTD_PASS_BYTES // (n * Wp * L * 8))))
+    out_d = v.empty((n, W, 2 + q.size), torch.float64)
+    out_i = v.empty((n, W, 3), torch.float64)
+    cols = v.empty((G * L, n * Wp), torch.float64)
+
+    def descriptors():
+        _hip.rtd_descriptors_dev(v.ptr, n, v.stride, E, Wp, ndim, d_lt.data_ptr(), L, d_q.data_ptr(), q.size,
+                                 out_d.data_ptr(), v.stream)
+
+    def integrals():
+        _hip.rtd_integrals_dev(v.ptr, n, v.stride, E, Wp, ndim, d_S.data_ptr(), d_nf.data_ptr(), out_i.data_ptr(), v.stream)
+
+    def columns():
+        for g0 in range(0, E, G):
+            _hip.rtd_columns_dev(v.ptr, n, v.stride, E, Wp, ndim, g0, min(E, g0 + G) - g0, d_lt.data_ptr(), L,
+                                 cols.data_ptr(), v.stream)
+    return descriptors, integrals, columns
+
+
+def timed_alternating(fs, reps=5):
+    """Median device time (ms) of each call of ``fs``, taken in turn ``reps`` times after one warm-up round."""
+    import torch
+    for f in fs:
+        f()
+    torch.cuda.synchronize()
+    times = [[] for _ in fs]
+    for _ in range(reps):
+        for f, ts in zip(fs, times):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            f()
+            b.record()
+            b.synchronize()
+            ts.append(a.elapsed_time(b))
+    return [float(np.median(ts)) for ts in times]
+
+
 def timed(f, reps):
     import torch
     for _ in range(2):
@@ -134,6 +186,10 @@ def run_shape(name, reps, subset):
                integrating_call_ms=ims, integrating_call_ms_median=ims_med,
                rtd_band_call_ms=bms, rtd_band_call_ms_median=bms_med,
                chain_bytes=int(8 * n * W * ndim), derived_bytes=int(8 * n * W * 3), columns_bytes=int(8 * n * W * L))
+    dms, ims3, cms = timed_alternating(entry_points(x, E, Wp, P, n, discard))
+    res.update(descriptors_ms=dms, integrals_ms=ims3, columns_ms=cms, descriptors_over_integrals=dms / ims3,
+               descriptors_over_columns=dms / cms, descriptor_bytes=int(8 * n * W * 5))
+    torch.cuda.empty_cache()
     res.update(host_path(x, E, Wp, P, discard, subset))
     del x
     torch.cuda.empty_cache()
@@ -162,7 +218,7 @@ def kernel_times(names, reps, outdir):
         import csv
         per = {}
         for row in csv.DictReader(open(files[0])):
-            m = re.search(r'\bk_(rtd_integrals|rtd_columns|moments_\w+|gather_columns\w*|segmented_select|percentile_lerp)'
+            m = re.search(r'\bk_(rtd_integrals|rtd_columns|rtd_descriptors|moments_\w+|gather_columns\w*|segmented_select|percentile_lerp)'
                           r'|DeviceSegmentedRadixSort|segmented_sort', row['Name'])
             if m:
                 key = m.group(0)
@@ -190,9 +246,11 @@ def main():
         E, Wp, P, stored, discard = SHAPES[args.child]
         x = make_chain(E, Wp, P, stored)
         integrating, band = device_calls(x, E, Wp, P, stored - discard, discard)
+        descriptors = entry_points(x, E, Wp, P, stored - discard, discard)[0]
         for _ in range(args.reps + 2):
             integrating()
             band()
+            descriptors()
         torch.cuda.synchronize()
         return
     import tempfile
@@ -211,6 +269,8 @@ def main():
             r['integrals_kernel_ms'] = k['k_rtd_integrals'] / p['launches_per_call']['k_rtd_integrals']
             r['integrals_chain_TBps'] = r['chain_bytes'] / (r['integrals_kernel_ms'] * 1e-3) / 1e12
             r['integrals_frac_of_hbm_peak'] = r['chain_bytes'] / (r['integrals_kernel_ms'] * 1e-3) / HBM_PEAK
+        if 'k_rtd_descriptors' in k:
+            r['descriptors_kernel_ms'] = k['k_rtd_descriptors']
         if 'k_rtd_columns' in k:         # all passes of one call
             r['columns_kernel_ms'] = k['k_rtd_columns']
             r['columns_write_TBps'] = r['columns_bytes'] / (k['k_rtd_columns'] * 1e-3) / 1e12

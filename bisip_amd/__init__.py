@@ -13,7 +13,7 @@ runs in hand-written gfx950 kernels behind the C ABI of ``include/bisip_hip.h``.
 
 from .autocorr import AutocorrError
 from .batch import SpectraBatch
-from .decomposition import INTEGRATING_NAMES, integrating_params, rtd
+from .decomposition import DESCRIPTOR_NAMES, INTEGRATING_NAMES, integrating_params, rtd, rtd_descriptors
 from .data import DataFiles
 from .models import (ColeCole, Dias2000, Inversion, PeltonColeCole, PolynomialDecomposition,
                      Shin2015)
@@ -22,4 +22,5 @@ from .utils import load_data, load_data_batch
 
 __all__ = ('Inversion', 'PolynomialDecomposition', 'PeltonColeCole', 'ColeCole', 'Dias2000',
            'Shin2015', 'DataFiles', 'SpectraBatch', 'EnsembleSampler', 'DeviceEnsembleSampler',
-           'load_data', 'load_data_batch', 'AutocorrError', 'INTEGRATING_NAMES', 'rtd', 'integrating_params')
+           'load_data', 'load_data_batch', 'AutocorrError', 'INTEGRATING_NAMES', 'rtd', 'integrating_params',
+           'rtd_descriptors', 'DESCRIPTOR_NAMES')

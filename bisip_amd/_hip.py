@@ -110,6 +110,11 @@ SYMBOLS = {
     'bisip_rtd_columns_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    'bisip_rtd_descriptors_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                 ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                                 ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    'bisip_rtd_descriptors_host': (ctypes.c_int, [_dp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                  ctypes.c_int, _dp, ctypes.c_int, _dp, ctypes.c_int, _dp]),
     'bisip_chain_range_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 3),
     'bisip_chain_histograms_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
@@ -911,6 +916,31 @@ def rtd_columns_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_
     _check(load_library().bisip_rtd_columns_dev(d_chain_ptr, int(n_samples), int(sample_stride), int(n_ensembles),
                                                 int(walkers_per_ensemble), int(ndim), int(first_ensemble), int(count),
                                                 d_log_tau_ptr, int(n_tau), d_cols_ptr, stream))
+
+
+def rtd_descriptors_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, d_log_tau_ptr,
+                        n_tau, d_q_ptr, n_q, d_out_ptr, stream=0):
+    """The relaxation descriptors (log_tau_peak, m_peak, log_tau_q1, ..., log_tau_qJ) of every used sample into d_out
+    (n_samples, n_ensembles * walkers_per_ensemble, 2 + n_q); device pointers (ints), asynchronous on ``stream``.  The
+    caller has checked ``q`` and the grid (bisip_amd.decomposition.checked_fractions, checked_grid)."""
+    _check(load_library().bisip_rtd_descriptors_dev(d_chain_ptr, int(n_samples), int(sample_stride), int(n_ensembles),
+                                                    int(walkers_per_ensemble), int(ndim), d_log_tau_ptr, int(n_tau),
+                                                    d_q_ptr, int(n_q), d_out_ptr, stream))
+
+
+def rtd_descriptors_host(chain, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, log_tau, q, offset=0):
+    """Host-only, no GPU: the rows of bisip_rtd_descriptors_dev by the same row function on the CPU
+    (bisip_rtd_descriptors_host).  ``chain``: a float64 array whose samples start ``offset`` doubles in and lie
+    ``sample_stride`` doubles apart; returns ``(n_samples, n_ensembles * walkers_per_ensemble, 2 + len(q))``."""
+    chain, log_tau, q = _c(chain).ravel(), _c(log_tau).ravel(), _c(q).ravel()
+    n, stride, rows, ndim, offset = int(n_samples), int(sample_stride), int(n_ensembles) * int(walkers_per_ensemble), int(ndim), int(offset)
+    if n < 1 or rows < 1 or offset < 0 or stride < rows * ndim or offset + (n - 1) * stride + rows * ndim > chain.size:
+        raise ValueError('the samples asked for lie outside the chain array')
+    out = np.empty((n, rows, 2 + q.size))
+    _check(load_library().bisip_rtd_descriptors_host(_p(chain[offset:]), n, stride, int(n_ensembles),
+                                                     int(walkers_per_ensemble), ndim, _p(log_tau), log_tau.size,
+                                                     _p(q), q.size, _p(out)))
+    return out
 
 
 def chain_range_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, d_out_ptr,

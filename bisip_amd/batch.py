@@ -52,7 +52,8 @@ def default_params(model, n_modes=1, poly_deg=5):
     return p
 
 
-class SpectraBatch(BatchCovariance, BatchIntervals, BatchEss, BatchResponse, BatchFitQuality, BatchLoo):
+class SpectraBatch(BatchCovariance, BatchIntervals, BatchEss, BatchResponse, BatchFitQuality, BatchLoo,
+                   decomposition.BatchRelaxation):
     """E spectra inverted together with the same model class.
 
     Args:

@@ -340,7 +340,7 @@ class Inversion(_plotlib, _utils.utils):
         return np.array(list(self.params.values()), dtype=np.float64).T
 
 
-class PolynomialDecomposition(DecompositionIntervals, Inversion):
+class PolynomialDecomposition(DecompositionIntervals, _decomp.DecompositionRelaxation, Inversion):
     """Debye / Warburg polynomial decomposition (reference: src/bisip/models.py:182-229).
 
     Args:

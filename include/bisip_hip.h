@@ -48,7 +48,7 @@ extern "C" {
  *    then chain_cov_dev and chain_best_sample_dev (+ _workspace), then forward_columns_kind_dev,
  *    forward_percentiles_kind and response_moments_dev (+ _workspace) with BISIP_RESPONSE_RI / _PA, then
  *    fit_quality_dev (+ _workspace), then reduced_emulate and ctx_reduced_operands, then q_columns_dev and
- *    loo_columns_dev (+ _workspace)
+ *    loo_columns_dev (+ _workspace), then rtd_descriptors_dev and rtd_descriptors_host
  *    came later under the same number (additions only: a caller that needs them looks the symbols up). */
 #define BISIP_ABI_VERSION 6
 
@@ -402,6 +402,29 @@ int bisip_rtd_integrals_dev(const double *d_chain, int64_t n_samples, int64_t sa
 int bisip_rtd_columns_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
                           int64_t walkers_per_ensemble, int ndim, int64_t first_ensemble, int64_t count,
                           const double *d_log_tau, int n_tau, double *d_cols, void *stream);
+
+/* The relaxation descriptors of every used sample: where the RTD of that sample peaks and the cumulative relaxation
+ * times at which the fractions q_1 ... q_J of its chargeability have accumulated (tau_10, tau_50, tau_90 of Nordsiek &
+ * Weller, 2008) -- what a reader of the tutorial's RTD plots (docs/tutorials/decomposition.ipynb, after the get_m cell)
+ * takes off the curve of the posterior mean by eye, here per posterior sample.  Same chain and theta conventions as
+ * bisip_rtd_integrals_dev; d_log_tau: (n_tau,) device doubles, strictly ascending (the caller's to check); d_q: (n_q,)
+ * device doubles in (0, 1] (the caller's to check), 1 <= n_q <= 8.  With m_l by Horner with fma as
+ * bisip_rtd_columns_dev, c_l = m_l > 0 ? m_l : 0, g_l = g_{l-1} + c_l in ascending l and total = g_{n_tau-1}:
+ * d_out (n_samples, n_ensembles*walkers_per_ensemble, 2 + n_q) = (log_tau_peak, m_peak, log_tau_q1, ..., log_tau_qJ);
+ * the peak is the first l of the largest m_l; log_tau_q = log_tau_0 if g_0 >= t = q * total, else
+ * fma((t - g_{k-1}) / c_k, log_tau_k - log_tau_{k-1}, log_tau_{k-1}) at the first k with g_k >= t.  A row whose total
+ * is not finite and positive gives NaN throughout.  The statement in full: bisip_amd/decomposition.py.  A chain of
+ * ndim = 2 + n_q that bisip_chain_moments_dev, bisip_chain_percentiles_dev and bisip_chain_hdi_dev summarise unchanged.
+ * Asynchronous on stream. */
+int bisip_rtd_descriptors_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+                              int64_t walkers_per_ensemble, int ndim, const double *d_log_tau, int n_tau,
+                              const double *d_q, int n_q, double *d_out, void *stream);
+
+/* Host-only, no GPU: the same rows by the same row function (csrc/rtd_descriptors.h) on the CPU -- every pointer a host
+ * pointer -- which is what tests/test_gpu_relaxation.py holds bisip_rtd_descriptors_dev to, bit for bit. */
+int bisip_rtd_descriptors_host(const double *chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+                               int64_t walkers_per_ensemble, int ndim, const double *log_tau, int n_tau,
+                               const double *q, int n_q, double *out);
 
 /* The shapes of the posterior of a chain resident in device memory: the counts the reference draws in
  * plot_histograms (src/bisip/plotlib.py:56-90: np.histogram of every parameter, bins = 25) and in plot_corner
