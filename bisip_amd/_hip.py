@@ -155,6 +155,15 @@ SYMBOLS = {
     'bisip_chain_rank_normalize_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                       ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                       ctypes.c_int64, ctypes.c_void_p]),
+    'bisip_chain_rank_normalize_folded_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                             ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                             ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    'bisip_chain_ess_squares_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                   ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    'bisip_chain_central_moments_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    'bisip_chain_central_moments_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                       ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 5),
     'bisip_column_percentiles_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     'bisip_column_percentiles_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, _dp, ctypes.c_int,
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
@@ -1095,6 +1104,42 @@ def chain_rank_normalize_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles,
     _check(load_library().bisip_chain_rank_normalize_dev(d_chain_ptr or None, int(n_samples), int(sample_stride),
                                                          int(n_ensembles), int(walkers_per_ensemble), int(ndim),
                                                          d_z_ptr or None, d_work_ptr or None, int(work_bytes), stream))
+
+
+def chain_rank_normalize_folded_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim,
+                                    d_center_ptr, d_z_ptr, d_work_ptr=0, work_bytes=0, stream=0):
+    """The rank-normalised folded chain, ``z_scale(abs(x - center))`` per ensemble with d_center (n_ensembles, ndim), into
+    d_z as chain_rank_normalize_dev; its workspace.  Device pointers (ints), asynchronous on ``stream``."""
+    _check(load_library().bisip_chain_rank_normalize_folded_dev(d_chain_ptr or None, int(n_samples), int(sample_stride),
+                                                                int(n_ensembles), int(walkers_per_ensemble), int(ndim),
+                                                                d_center_ptr or None, d_z_ptr or None, d_work_ptr or None,
+                                                                int(work_bytes), stream))
+
+
+def chain_ess_squares_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, splits, d_center_ptr,
+                          d_ess_ptr, d_work_ptr=0, work_bytes=0, stream=0):
+    """chain_ess_dev of the series ``(x - center) * (x - center)`` with d_center (n_ensembles, ndim), into d_ess
+    (n_ensembles, ndim); workspace: chain_ess_workspace without thresholds.  Device pointers (ints), asynchronous on
+    ``stream``."""
+    _check(load_library().bisip_chain_ess_squares_dev(d_chain_ptr or None, int(n_samples), int(sample_stride),
+                                                      int(n_ensembles), int(walkers_per_ensemble), int(ndim), int(splits),
+                                                      d_center_ptr or None, d_ess_ptr or None, d_work_ptr or None,
+                                                      int(work_bytes), stream))
+
+
+def chain_central_moments_workspace(n_samples, n_ensembles, ndim):
+    """DOUBLES of device scratch chain_central_moments_dev needs: twice chain_moments_workspace."""
+    return int(load_library().bisip_chain_central_moments_workspace(int(n_samples), int(n_ensembles), int(ndim)))
+
+
+def chain_central_moments_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, d_center_ptr,
+                              d_m2_ptr, d_m4_ptr, d_work_ptr, stream=0):
+    """The means of ``(x - center)**2`` and ``(x - center)**4`` of every (ensemble, parameter) into d_m2 and d_m4
+    (n_ensembles, ndim), d_center (n_ensembles, ndim).  Device pointers (ints), asynchronous on ``stream``."""
+    _check(load_library().bisip_chain_central_moments_dev(d_chain_ptr or None, int(n_samples), int(sample_stride),
+                                                          int(n_ensembles), int(walkers_per_ensemble), int(ndim),
+                                                          d_center_ptr or None, d_m2_ptr or None, d_m4_ptr or None,
+                                                          d_work_ptr or None, stream))
 
 
 def ensemble_gram_workspace(W, ndim):

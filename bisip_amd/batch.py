@@ -12,6 +12,7 @@ import numpy as np
 from . import _hip, decomposition
 from .autocorr import AutocorrError
 from .covariance import BatchCovariance
+from .diagnostics import BatchDiagnostics
 from .ess import BatchEss
 from .fitquality import BatchFitQuality
 from .interval import BatchIntervals
@@ -52,7 +53,7 @@ def default_params(model, n_modes=1, poly_deg=5):
     return p
 
 
-class SpectraBatch(BatchCovariance, BatchIntervals, BatchEss, BatchResponse, BatchFitQuality, BatchLoo,
+class SpectraBatch(BatchCovariance, BatchIntervals, BatchEss, BatchDiagnostics, BatchResponse, BatchFitQuality, BatchLoo,
                    decomposition.BatchRelaxation):
     """E spectra inverted together with the same model class.
 

@@ -10,7 +10,8 @@ bisip_chain_percentiles_dev); the others are in bisip_amd.autocorr, bisip_amd.hi
 
 import numpy as np
 
-__all__ = ('used_range', 'ChainView', 'device_moments', 'device_percentiles', 'moment_splits', 'ordered_moments')
+__all__ = ('used_range', 'ChainView', 'device_moments', 'device_percentiles', 'moment_splits', 'ordered_sweep',
+           'ordered_moments')
 
 
 def used_range(n_total, discard, thin):
@@ -183,6 +184,55 @@ def exact_fma(a, b, c):
     return -0.0 if r == 0.0 and exact < 0 else r
 
 
+def _ensemble_rows(x, n_ensembles):
+    """``(v (n, E, Wp * ndim), n, E, Wp, ndim, lanes)`` of a chain ``(n, E * Wp, ndim)``: every ensemble's doubles of a
+    sample as the moments kernels sweep them, and how many of their 256 lanes work."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim != 3:
+        raise ValueError('the chain must be (n, walkers, ndim)')
+    n, W, ndim = x.shape
+    E = int(n_ensembles)
+    if n < 1 or W < 1 or ndim < 1 or E < 1 or W % E:
+        raise ValueError(f'a chain {x.shape} does not divide into {E} ensembles')
+    lanes = (MOMENT_THREADS // ndim) * ndim
+    if lanes < 1:
+        raise ValueError(f'ndim={ndim} out of range')
+    return x.reshape(n, E, (W // E) * ndim), n, E, W // E, ndim, lanes
+
+
+def ordered_sweep(v, ndim, lanes, term):
+    """One sweep of the moments kernels over ``v (n, E, Wp * ndim)`` in their stated order, ``(E, ndim)``: ``term(acc (E,
+    k), values (E, k), k)`` gives the accumulators of lanes ``0 ... k - 1`` after one more value each (lane ``t`` holds
+    parameter ``t % ndim``)."""
+    n, E, length = v.shape
+    splits = moment_splits(n, E)
+    # the doubles i ... i + k - 1 of a sample go to lanes 0 ... k - 1 (a lane beyond the last double adds nothing)
+    turns = [(i, min(lanes, length - i)) for i in range(0, length, lanes)]
+
+    def add(acc, s, i, k):
+        acc[:, :k] = term(acc[:, :k], v[s, :, i:i + k], k)
+
+    total = np.zeros((E, ndim))
+    for sp in range(splits):
+        s, s1 = n * sp // splits, n * (sp + 1) // splits
+        acc = np.zeros((4, E, lanes))
+        while s + 4 <= s1:
+            for i, k in turns:                       # for each double of the lane in turn, sample s + j to j
+                for j in range(4):
+                    add(acc[j], s + j, i, k)
+            s += 4
+        while s < s1:
+            for i, k in turns:
+                add(acc[0], s, i, k)
+            s += 1
+        lane = (acc[0] + acc[1]) + (acc[2] + acc[3])
+        part = np.zeros((E, ndim))
+        for k in range(lanes // ndim):
+            part = part + lane[:, k * ndim:(k + 1) * ndim]
+        total = total + part
+    return total
+
+
 def ordered_moments(x, n_ensembles=1):
     """``(mean, std)``, ``(n_ensembles, ndim)`` each, of a chain ``(n, n_ensembles * Wp, ndim)`` with the bits
     bisip_chain_moments_dev produces, in the order include/bisip_hip.h states: samples in ``moment_splits`` ranges; lane
@@ -191,59 +241,21 @@ def ordered_moments(x, n_ensembles=1):
     lanes of a parameter, then splits, in ascending order.  The second pass is ``fma(d, d, acc)`` with ``d = x - mean``,
     taken exactly value by value in Python (``exact_fma``): some 10 us per value, so this is for chains of a few ten
     thousand values -- the small shapes of the tests -- and not for a fit's."""
-    x = np.ascontiguousarray(x, dtype=np.float64)
-    if x.ndim != 3:
-        raise ValueError('the chain must be (n, walkers, ndim)')
-    n, W, ndim = x.shape
-    E = int(n_ensembles)
-    if n < 1 or W < 1 or ndim < 1 or E < 1 or W % E:
-        raise ValueError(f'a chain {x.shape} does not divide into {E} ensembles')
-    Wp = W // E
-    length = Wp * ndim                                   # doubles of an ensemble per sample
-    lanes = (MOMENT_THREADS // ndim) * ndim
-    if lanes < 1:
-        raise ValueError(f'ndim={ndim} out of range')
-    splits = moment_splits(n, E)
-    v = x.reshape(n, E, length)
+    v, n, E, Wp, ndim, lanes = _ensemble_rows(x, n_ensembles)
     fma = np.frompyfunc(exact_fma, 3, 1)
 
-    # the doubles i ... i + k - 1 of a sample go to lanes 0 ... k - 1 (a lane beyond the last double adds nothing)
-    turns = [(i, min(lanes, length - i)) for i in range(0, length, lanes)]
+    def squares(mean):
+        m = np.tile(mean, (1, lanes // ndim))        # lane t: parameter t % ndim
 
-    def sweep(mean):
-        m = None if mean is None else np.tile(mean, (1, lanes // ndim))     # lane t: parameter t % ndim
-
-        def add(acc, s, i, k):
-            if m is None:
-                acc[:, :k] = acc[:, :k] + v[s, :, i:i + k]
-            else:
-                d = v[s, :, i:i + k] - m[:, :k]
-                acc[:, :k] = fma(d, d, acc[:, :k]).astype(np.float64)
-
-        total = np.zeros((E, ndim))
-        for sp in range(splits):
-            s, s1 = n * sp // splits, n * (sp + 1) // splits
-            acc = np.zeros((4, E, lanes))
-            while s + 4 <= s1:
-                for i, k in turns:                       # for each double of the lane in turn, sample s + j to j
-                    for j in range(4):
-                        add(acc[j], s + j, i, k)
-                s += 4
-            while s < s1:
-                for i, k in turns:
-                    add(acc[0], s, i, k)
-                s += 1
-            lane = (acc[0] + acc[1]) + (acc[2] + acc[3])
-            part = np.zeros((E, ndim))
-            for k in range(lanes // ndim):
-                part = part + lane[:, k * ndim:(k + 1) * ndim]
-            total = total + part
-        return total
+        def term(acc, values, k):
+            d = values - m[:, :k]
+            return fma(d, d, acc).astype(np.float64)
+        return term
 
     with np.errstate(all='ignore'):
         count = float(n) * float(Wp)
-        mean = sweep(None) / count
-        std = np.sqrt(sweep(mean) / count)
+        mean = ordered_sweep(v, ndim, lanes, lambda acc, values, k: acc + values) / count
+        std = np.sqrt(ordered_sweep(v, ndim, lanes, squares(mean)) / count)
     return mean, std
 
 

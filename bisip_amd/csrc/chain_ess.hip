@@ -1,12 +1,12 @@
 // chain_ess.hip -- effective sample size of a device-resident chain (bisip_chain_ess_dev) and the rank-normalisation
-// that its bulk form is taken of (bisip_chain_rank_normalize_dev).  bisip_amd/ess.py holds the definitions in NumPy
+// that its bulk form is taken of (bisip_chain_rank_normalize_dev; folded about a centre: ..._folded_dev).  bisip_amd/ess.py holds the definitions in NumPy
 // (ess_of_chains, z_scale): the estimator of Vehtari, Gelman, Simpson, Carpenter and Buerkner (2021) as Stan and ArviZ
 // compute it.
 //
 // A half is the whole series (splits = 1, L = n) or its first and last L = n / 2 samples (splits = 2; the middle sample of
 // an odd n is in neither).  A column j in [0, C), C = E * Wp * ndim, is one (ensemble, walker, parameter); a series is
-// (threshold v, half, column): the values of the half, or with thresholds the indicator x <= thr[v, e, d] ? 1 : 0,
-// applied on load.  A pair p = (v * E + e) * ndim + d owns the M = splits * Wp chains c = half * Wp + w.
+// (threshold v, half, column): the values of the half, or with thresholds the indicator x <= thr[v, e, d] ? 1 : 0, or
+// with a centre (bisip_chain_ess_squares_dev) the square (x - c[e, d]) * (x - c[e, d]), applied on load.  A pair p = (v * E + e) * ndim + d owns the M = splits * Wp chains c = half * Wp + w.
 //   1. k_ess_prep: mean of every series from sums shifted by its first sample (a constant chain has mean exactly its
 //      value and centred samples exactly 0), its min and max (NaN when a value is not finite); one workgroup per tile of
 //      64 series, the samples split over its 16 waves and the partial sums added in a fixed order;
@@ -38,7 +38,8 @@ struct EssArgs {
     long long n, stride, E, Wp, C;     // C = E*Wp*ndim columns
     long long L, start1;               // samples of a half, first sample of half 1
     int ndim, splits, nthr;            // nthr >= 1 series sets (thr null: the values themselves)
-    const double *thr;                 // (nthr, E, ndim) or null
+    int mode;                          // ES_VALUES, ES_INDICATOR or ES_SQUARES
+    const double *thr;                 // (nthr, E, ndim) thresholds, (E, ndim) centres (nthr = 1) or null
     long long Lr, k0;                  // lags per round, first lag of this round
     double *mean, *cmin, *cmax;        // (nthr*splits*C,) per series
     double *R;                         // (nthr*splits*C, Lr): raw lag sums of the round
@@ -50,7 +51,19 @@ struct EssArgs {
     double *ess;                       // (nthr, E, ndim)
 };
 
-__device__ __forceinline__ double es_value(double x, bool ind, double thr) { return ind ? (x <= thr ? 1.0 : 0.0) : x; }
+// the series on load: the value, the indicator of a threshold, or the square about a centre -- one subtraction and one
+// multiplication, each rounded (nothing is contracted: -ffp-contract=off)
+enum { ES_VALUES = 0, ES_INDICATOR = 1, ES_SQUARES = 2 };
+
+__device__ __forceinline__ double es_value(double x, int mode, double thr)
+{
+    if (mode == ES_INDICATOR) return x <= thr ? 1.0 : 0.0;
+    if (mode == ES_SQUARES) {
+        const double d = x - thr;
+        return d * d;
+    }
+    return x;
+}
 
 // series z * C + j of chain c of pair (v, e, d)
 __device__ __forceinline__ long long es_series(const EssArgs &a, long long v, long long e, int d, long long c)
@@ -73,17 +86,18 @@ __global__ __launch_bounds__(LAG_PREP_WAVES * 64) void k_ess_prep(const EssArgs 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long j = (long long)blockIdx.x * LAG_TILE + lane;
     const long long z = blockIdx.y, v = z / a.splits, half = z - v * a.splits;
-    const bool live = j < a.C, ind = a.thr != nullptr;
+    const bool live = j < a.C;
+    const int mode = a.mode;
     double thr = 0.0, c = 0.0, s = 0.0, lo = __builtin_inf(), hi = -__builtin_inf();
     int bad = 0;
     if (live) {
         const long long e = j / (a.Wp * a.ndim);
         const int d = (int)(j % a.ndim);
-        if (ind) thr = a.thr[(v * a.E + e) * a.ndim + d];
+        if (mode) thr = a.thr[(v * a.E + e) * a.ndim + d];
         const double *x = a.chain + (half ? a.start1 : 0) * a.stride + j;
-        c = es_value(x[0], ind, thr);
+        c = es_value(x[0], mode, thr);
         for (long long t = wave; t < a.L; t += LAG_PREP_WAVES) {
-            const double val = es_value(x[t * a.stride], ind, thr);
+            const double val = es_value(x[t * a.stride], mode, thr);
             s += val - c;
             lo = fmin(lo, val);
             hi = fmax(hi, val);
@@ -119,7 +133,8 @@ __global__ __launch_bounds__(LAG_WAVES * 64) void k_ess_lags(const EssArgs a)
     if (kb >= a.L) return;
     const long long j = (long long)blockIdx.x * LAG_TILE + lane;
     const long long z = blockIdx.z, v = z / a.splits, half = z - v * a.splits;
-    const bool live = j < a.C, ind = a.thr != nullptr;
+    const bool live = j < a.C;
+    const int mode = a.mode;
     // the tile leaves when every series in it belongs to a pair whose sequence has ended
     // (the same 64 lanes in every wave: the exit is uniform over the workgroup)
     bool open = false;
@@ -129,12 +144,12 @@ __global__ __launch_bounds__(LAG_WAVES * 64) void k_ess_lags(const EssArgs a)
         const int d = (int)(j % a.ndim);
         const long long p = (v * a.E + e) * a.ndim + d;
         open = a.done[p] == 0;
-        if (ind) thr = a.thr[p];
+        if (mode) thr = a.thr[p];
     }
     if (!__any(open)) return;
     const double m = live ? a.mean[z * a.C + j] : 0.0;
     const double *x = a.chain + (half ? a.start1 : 0) * a.stride + (live ? j : 0);
-    auto y = [&](long long t) { return live && t < a.L ? es_value(x[t * a.stride], ind, thr) - m : 0.0; };
+    auto y = [&](long long t) { return live && t < a.L ? es_value(x[t * a.stride], mode, thr) - m : 0.0; };
 
     double acc[LAGS_WAVE];
 #pragma unroll
@@ -339,6 +354,48 @@ Layout ess_layout(long long n, long long E, long long Wp, int ndim, int splits, 
     return l;
 }
 
+// what bisip_chain_ess_dev and bisip_chain_ess_squares_dev share: the checks of the shape, the layout and the rounds.
+// d_aux: the thresholds (n_threshold of them), the centres (n_threshold = 0) or null.
+int ess_run(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+            int64_t walkers_per_ensemble, int ndim, int splits, int mode, const double *d_aux, int n_threshold,
+            double *d_ess, void *d_work, int64_t work_bytes, void *stream)
+{
+    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
+    if (splits != 1 && splits != 2) return fail(BISIP_EINVAL, "splits=%d: 1 or 2", splits);
+    if (n_samples < 2 * splits)
+        return fail(BISIP_EINVAL, "n_samples=%lld: a chain needs 2 samples, a half too", (long long)n_samples);
+    if (!ess_shape_ok(n_samples, n_ensembles, walkers_per_ensemble, ndim, splits, n_threshold))
+        return fail(BISIP_EINVAL, "bad chain shape");
+    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
+        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
+    const Layout l = ess_layout(n_samples, n_ensembles, walkers_per_ensemble, ndim, splits, n_threshold);
+    if (work_bytes < (int64_t)l.total)
+        return fail(BISIP_EINVAL, "workspace of %lld bytes, need %zu", (long long)work_bytes, l.total);
+    char *base = (char *)d_work;
+    EssArgs a{};
+    a.chain = d_chain; a.n = n_samples; a.stride = sample_stride; a.E = n_ensembles; a.Wp = walkers_per_ensemble;
+    a.C = l.C; a.L = l.L; a.start1 = n_samples - l.L; a.ndim = ndim; a.splits = splits;
+    a.nthr = n_threshold > 0 ? n_threshold : 1;
+    a.mode = mode; a.thr = d_aux; a.Lr = l.Lr; a.k0 = 0;
+    a.mean = (double *)(base + l.mean); a.cmin = (double *)(base + l.cmin); a.cmax = (double *)(base + l.cmax);
+    a.R = (double *)(base + l.R); a.part = (double *)(base + l.part); a.G = l.G;
+    a.state = (double *)(base + l.state); a.t = (long long *)(base + l.t); a.done = (int *)(base + l.done);
+    a.ess = d_ess;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_ess_init, dim3((unsigned)((l.P + 255) / 256)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_ess_prep, dim3((unsigned)l.tiles, (unsigned)l.Z), dim3(LAG_PREP_WAVES * 64), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    for (long long k0 = 0; k0 < l.L; k0 += l.Lr) {
+        a.k0 = k0;
+        const long long nb = round_blocks(l.L, k0, l.Lr);
+        hipLaunchKernelGGL(k_ess_lags, dim3((unsigned)l.tiles, (unsigned)nb, (unsigned)l.Z), dim3(LAG_WAVES * 64), 0, st, a);
+        hipLaunchKernelGGL(k_ess_chain_sums, dim3((unsigned)l.P, (unsigned)l.G), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(k_ess_scan, dim3((unsigned)l.P), dim3(64), 0, st, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return BISIP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // rank-normalisation
 // ---------------------------------------------------------------------------------------------------------------
@@ -396,12 +453,22 @@ struct RankArgs {
     const double *sorted;      // (E*ndim, N): every column in ascending order
     long long N;               // n * Wp values of a column
     double *z;                 // (n, E*Wp, ndim)
+    const double *center;      // (E, ndim): the ranks are those of fabs(x - center); null: of x itself
 };
+
+// The fold of bisip_chain_rank_normalize_folded_dev on the gathered columns, in place, before they are sorted: one
+// thread per value, column e * ndim + q about center[e * ndim + q].  One IEEE subtraction and fabs, as in k_rank_z.
+__global__ __launch_bounds__(256) void k_fold_columns(double *cols, long long N, long long items, const double *center)
+{
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= items) return;
+    cols[idx] = fabs(cols[idx] - center[idx / N]);
+}
 
 // One thread per chain element, in the order of the chain: both sides coalesced.  below = how many values of its sorted
 // column are smaller, upto = how many are not larger (two binary searches: no index goes through the sort); its ties
 // hold the ranks below + 1 ... upto, whose mean is (below + upto + 1) / 2.  The sort puts whatever is not finite at one
-// of the two ends of the column.
+// of the two ends of the column.  With a centre the element is folded as its column was, by the same two operations.
 __global__ __launch_bounds__(256) void k_rank_z(const RankArgs a)
 {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -410,7 +477,8 @@ __global__ __launch_bounds__(256) void k_rank_z(const RankArgs a)
     const long long s = idx / row, rest = idx - s * row, r = rest / a.ndim, e = r / a.Wp;
     const int q = (int)(rest - r * a.ndim);
     const double *__restrict__ col = a.sorted + (e * a.ndim + q) * a.N;
-    const double x = a.chain[s * a.stride + rest];
+    double x = a.chain[s * a.stride + rest];
+    if (a.center) x = fabs(x - a.center[e * a.ndim + q]);
     double out = __builtin_nan("");
     if (__builtin_isfinite(col[0]) && __builtin_isfinite(col[a.N - 1])) {
         long long lo = 0, hi = a.N;
@@ -449,6 +517,37 @@ bool rank_plan(int64_t n, int64_t E, int64_t Wp, int ndim, RankPlan &p)
     return true;
 }
 
+// what bisip_chain_rank_normalize_dev (d_center null) and bisip_chain_rank_normalize_folded_dev share
+int rank_run(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+             int64_t walkers_per_ensemble, int ndim, const double *d_center, double *d_z, void *d_work, int64_t work_bytes,
+             void *stream)
+{
+    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
+    if (n_samples < 1 || n_ensembles < 1 || walkers_per_ensemble < 1) return fail(BISIP_EINVAL, "bad chain shape");
+    RankPlan p{};
+    if (!rank_plan(n_samples, n_ensembles, walkers_per_ensemble, ndim, p))
+        return fail(BISIP_EUNSUPPORTED, "chain exceeds the 2^31 items of one sort");
+    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
+        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
+    if (work_bytes < (int64_t)p.need)
+        return fail(BISIP_EINVAL, "workspace of %lld bytes, need %zu", (long long)work_bytes, p.need);
+    hipStream_t st = (hipStream_t)stream;
+    char *base = (char *)d_work;
+    double *cols = (double *)base, *sorted = (double *)(base + p.col_bytes);
+    int rc = gather_columns(d_chain, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, cols, st);
+    if (rc != BISIP_OK) return rc;
+    if (d_center) {
+        hipLaunchKernelGGL(k_fold_columns, dim3((unsigned)((p.items + 255) / 256)), dim3(256), 0, st, cols, p.N, p.items, d_center);
+        HIP_TRY(hipGetLastError());
+    }
+    rc = sort_segments(base + 2 * p.col_bytes, p.temp_bytes, cols, sorted, p.items, p.columns, p.N, st);
+    if (rc != BISIP_OK) return rc;
+    const RankArgs ra{d_chain, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, sorted, p.N, d_z, d_center};
+    hipLaunchKernelGGL(k_rank_z, dim3((unsigned)((p.items + 255) / 256)), dim3(256), 0, st, ra);
+    HIP_TRY(hipGetLastError());
+    return BISIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -465,42 +564,19 @@ int bisip_chain_ess_dev(const double *d_chain, int64_t n_samples, int64_t sample
                         double *d_ess, void *d_work, int64_t work_bytes, void *stream)
 {
     if (!d_chain || !d_ess || !d_work) return fail(BISIP_EINVAL, "null argument");
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
-    if (splits != 1 && splits != 2) return fail(BISIP_EINVAL, "splits=%d: 1 or 2", splits);
     if (d_threshold ? (n_threshold < 1 || n_threshold > ESS_MAX_THRESHOLDS) : n_threshold != 0)
         return fail(BISIP_EINVAL, "n_threshold=%d: 1 ... %d with thresholds, 0 without", n_threshold, ESS_MAX_THRESHOLDS);
-    if (n_samples < 2 * splits)
-        return fail(BISIP_EINVAL, "n_samples=%lld: a chain needs 2 samples, a half too", (long long)n_samples);
-    if (!ess_shape_ok(n_samples, n_ensembles, walkers_per_ensemble, ndim, splits, n_threshold))
-        return fail(BISIP_EINVAL, "bad chain shape");
-    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
-    const Layout l = ess_layout(n_samples, n_ensembles, walkers_per_ensemble, ndim, splits, n_threshold);
-    if (work_bytes < (int64_t)l.total)
-        return fail(BISIP_EINVAL, "workspace of %lld bytes, need %zu", (long long)work_bytes, l.total);
-    char *base = (char *)d_work;
-    EssArgs a{};
-    a.chain = d_chain; a.n = n_samples; a.stride = sample_stride; a.E = n_ensembles; a.Wp = walkers_per_ensemble;
-    a.C = l.C; a.L = l.L; a.start1 = n_samples - l.L; a.ndim = ndim; a.splits = splits;
-    a.nthr = n_threshold > 0 ? n_threshold : 1;
-    a.thr = d_threshold; a.Lr = l.Lr; a.k0 = 0;
-    a.mean = (double *)(base + l.mean); a.cmin = (double *)(base + l.cmin); a.cmax = (double *)(base + l.cmax);
-    a.R = (double *)(base + l.R); a.part = (double *)(base + l.part); a.G = l.G;
-    a.state = (double *)(base + l.state); a.t = (long long *)(base + l.t); a.done = (int *)(base + l.done);
-    a.ess = d_ess;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_ess_init, dim3((unsigned)((l.P + 255) / 256)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_ess_prep, dim3((unsigned)l.tiles, (unsigned)l.Z), dim3(LAG_PREP_WAVES * 64), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    for (long long k0 = 0; k0 < l.L; k0 += l.Lr) {
-        a.k0 = k0;
-        const long long nb = round_blocks(l.L, k0, l.Lr);
-        hipLaunchKernelGGL(k_ess_lags, dim3((unsigned)l.tiles, (unsigned)nb, (unsigned)l.Z), dim3(LAG_WAVES * 64), 0, st, a);
-        hipLaunchKernelGGL(k_ess_chain_sums, dim3((unsigned)l.P, (unsigned)l.G), dim3(64), 0, st, a);
-        hipLaunchKernelGGL(k_ess_scan, dim3((unsigned)l.P), dim3(64), 0, st, a);
-        HIP_TRY(hipGetLastError());
-    }
-    return BISIP_OK;
+    return ess_run(d_chain, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, splits,
+                   d_threshold ? ES_INDICATOR : ES_VALUES, d_threshold, n_threshold, d_ess, d_work, work_bytes, stream);
+}
+
+int bisip_chain_ess_squares_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+                                int64_t walkers_per_ensemble, int ndim, int splits, const double *d_center, double *d_ess,
+                                void *d_work, int64_t work_bytes, void *stream)
+{
+    if (!d_chain || !d_center || !d_ess || !d_work) return fail(BISIP_EINVAL, "null argument");
+    return ess_run(d_chain, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, splits, ES_SQUARES, d_center, 0,
+                   d_ess, d_work, work_bytes, stream);
 }
 
 int64_t bisip_chain_rank_normalize_workspace(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim)
@@ -515,26 +591,17 @@ int bisip_chain_rank_normalize_dev(const double *d_chain, int64_t n_samples, int
                                    void *stream)
 {
     if (!d_chain || !d_z || !d_work) return fail(BISIP_EINVAL, "null argument");
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
-    if (n_samples < 1 || n_ensembles < 1 || walkers_per_ensemble < 1) return fail(BISIP_EINVAL, "bad chain shape");
-    RankPlan p{};
-    if (!rank_plan(n_samples, n_ensembles, walkers_per_ensemble, ndim, p))
-        return fail(BISIP_EUNSUPPORTED, "chain exceeds the 2^31 items of one sort");
-    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
-    if (work_bytes < (int64_t)p.need)
-        return fail(BISIP_EINVAL, "workspace of %lld bytes, need %zu", (long long)work_bytes, p.need);
-    hipStream_t st = (hipStream_t)stream;
-    char *base = (char *)d_work;
-    double *cols = (double *)base, *sorted = (double *)(base + p.col_bytes);
-    int rc = gather_columns(d_chain, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, cols, st);
-    if (rc != BISIP_OK) return rc;
-    rc = sort_segments(base + 2 * p.col_bytes, p.temp_bytes, cols, sorted, p.items, p.columns, p.N, st);
-    if (rc != BISIP_OK) return rc;
-    const RankArgs ra{d_chain, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, sorted, p.N, d_z};
-    hipLaunchKernelGGL(k_rank_z, dim3((unsigned)((p.items + 255) / 256)), dim3(256), 0, st, ra);
-    HIP_TRY(hipGetLastError());
-    return BISIP_OK;
+    return rank_run(d_chain, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, nullptr, d_z, d_work,
+                    work_bytes, stream);
+}
+
+int bisip_chain_rank_normalize_folded_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride,
+                                          int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim,
+                                          const double *d_center, double *d_z, void *d_work, int64_t work_bytes, void *stream)
+{
+    if (!d_chain || !d_center || !d_z || !d_work) return fail(BISIP_EINVAL, "null argument");
+    return rank_run(d_chain, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, d_center, d_z, d_work,
+                    work_bytes, stream);
 }
 
 }  // extern "C"

@@ -1,4 +1,6 @@
-// chain_moments.hip -- mean and standard deviation of a device-resident chain (bisip_chain_moments_dev).
+// chain_moments.hip -- mean and standard deviation of a device-resident chain (bisip_chain_moments_dev), and its second and
+// fourth moments about a given centre (bisip_chain_central_moments_dev; bisip_amd.diagnostics: the Monte-Carlo error of the
+// standard deviation), in the order of the former's second pass.
 //
 // The reference summarises a fit with np.mean / np.std over the flattened chain
 // (src/bisip/utils.py:55-85, get_param_mean / get_param_std).  For a batch of spectra the
@@ -92,6 +94,82 @@ __global__ __launch_bounds__(256) void k_moments_finish(const MomentArgs a)
     else a.mean[idx] = sum / cnt;
 }
 
+// bisip_chain_central_moments_dev: the means of (x - c)^2 and (x - c)^4 about a given centre c (E, ndim), in the order of
+// pass 1 above -- the same splits, lanes, four accumulators per lane (here four per moment) and ascending combination.
+// Per value d = x - c and q = d * d round once each; acc2 = fma(d, d, acc2), acc4 = fma(q, q, acc4).
+struct CentralArgs {
+    const double *chain;
+    long long n_samples, sample_stride, E, Wp;
+    int ndim, splits;
+    const double *center;    // (E, ndim)
+    double *m2, *m4;         // (E, ndim)
+    double *partial;         // (2, E, splits, ndim) workspace: the sums of squares, then of fourth powers
+};
+
+__global__ __launch_bounds__(256) void k_central_partial(const CentralArgs a)
+{
+    __shared__ double part2[256], part4[256];
+    const int e = blockIdx.x, sp = blockIdx.y;
+    const int per = 256 / a.ndim, lanes = per * a.ndim;
+    const int t = threadIdx.x;
+    const int q = t % a.ndim;
+    const long long s0 = a.n_samples * sp / a.splits, s1 = a.n_samples * (sp + 1) / a.splits;
+    const long long len = a.Wp * a.ndim;
+    const double *base = a.chain + (long long)e * len;
+    const double c = a.center[(long long)e * a.ndim + q];
+    double a2[4] = {0.0, 0.0, 0.0, 0.0}, a4[4] = {0.0, 0.0, 0.0, 0.0};
+    auto add = [&](double &s2, double &s4, double x) {
+        const double d = x - c, dd = d * d;
+        s2 = fma(d, d, s2);
+        s4 = fma(dd, dd, s4);
+    };
+    if (t < lanes) {
+        long long s = s0;
+        for (; s + 4 <= s1; s += 4) {
+            const double *p = base + s * a.sample_stride;
+            for (long long i = t; i < len; i += lanes) {
+                const double x0 = __builtin_nontemporal_load(p + i), x1 = __builtin_nontemporal_load(p + a.sample_stride + i);
+                const double x2 = __builtin_nontemporal_load(p + 2 * a.sample_stride + i), x3 = __builtin_nontemporal_load(p + 3 * a.sample_stride + i);
+                add(a2[0], a4[0], x0); add(a2[1], a4[1], x1); add(a2[2], a4[2], x2); add(a2[3], a4[3], x3);
+            }
+        }
+        for (; s < s1; ++s) {
+            const double *p = base + s * a.sample_stride;
+            for (long long i = t; i < len; i += lanes) add(a2[0], a4[0], __builtin_nontemporal_load(p + i));
+        }
+    }
+    part2[t] = (a2[0] + a2[1]) + (a2[2] + a2[3]);
+    part4[t] = (a4[0] + a4[1]) + (a4[2] + a4[3]);
+    __syncthreads();
+    if (t < a.ndim) {
+        double sum2 = 0.0, sum4 = 0.0;
+        for (int k = 0; k < per; ++k) {
+            sum2 += part2[k * a.ndim + t];
+            sum4 += part4[k * a.ndim + t];
+        }
+        const long long at = ((long long)e * a.splits + sp) * a.ndim + t;
+        a.partial[at] = sum2;
+        a.partial[a.E * a.splits * a.ndim + at] = sum4;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_central_finish(const CentralArgs a)
+{
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;  // (e, q)
+    if (idx >= a.E * a.ndim) return;
+    const long long e = idx / a.ndim;
+    const int q = (int)(idx % a.ndim);
+    const double *p4 = a.partial + a.E * a.splits * a.ndim;
+    double sum2 = 0.0, sum4 = 0.0;
+    for (int sp = 0; sp < a.splits; ++sp) {
+        sum2 += a.partial[(e * a.splits + sp) * a.ndim + q];
+        sum4 += p4[(e * a.splits + sp) * a.ndim + q];
+    }
+    const double cnt = (double)a.n_samples * (double)a.Wp;
+    a.m2[idx] = sum2 / cnt;
+    a.m4[idx] = sum4 / cnt;
+}
+
 static int moment_splits(int64_t n_samples, int64_t E)
 {
     // enough workgroups to fill the chip (256 CUs x 16), at least four samples each
@@ -130,6 +208,33 @@ int bisip_chain_moments_dev(const double *d_chain, int64_t n_samples, int64_t sa
     hipLaunchKernelGGL(k_moments_finish<0>, fin, dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_moments_partial<1>, grid, dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_moments_finish<1>, fin, dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return BISIP_OK;
+}
+
+int64_t bisip_chain_central_moments_workspace(int64_t n_samples, int64_t n_ensembles, int ndim)
+{
+    return 2 * bisip_chain_moments_workspace(n_samples, n_ensembles, ndim);
+}
+
+int bisip_chain_central_moments_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride,
+                                    int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim,
+                                    const double *d_center, double *d_m2, double *d_m4, double *d_work, void *stream)
+{
+    if (!d_chain || !d_center || !d_m2 || !d_m4 || !d_work) return fail(BISIP_EINVAL, "null argument");
+    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
+    if (n_samples < 1 || n_ensembles < 1 || n_ensembles > 0x7fffffffLL || walkers_per_ensemble < 1)
+        return fail(BISIP_EINVAL, "bad chain shape");
+    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
+        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
+    CentralArgs a;
+    a.chain = d_chain; a.n_samples = n_samples; a.sample_stride = sample_stride;
+    a.E = n_ensembles; a.Wp = walkers_per_ensemble; a.ndim = ndim;
+    a.splits = moment_splits(n_samples, n_ensembles);
+    a.center = d_center; a.m2 = d_m2; a.m4 = d_m4; a.partial = d_work;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_central_partial, dim3((unsigned)n_ensembles, (unsigned)a.splits), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_central_finish, dim3((unsigned)((n_ensembles * ndim + 255) / 256)), dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
     return BISIP_OK;
 }

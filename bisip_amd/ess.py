@@ -266,13 +266,20 @@ def round_lags(n, n_ensembles, walkers_per_ensemble, ndim, split=True, n_thresho
     return 64 * max(1, min(-(-L // 64), -(-512 // tiles), 65535))
 
 
-def device_rank_normalize(view):
+def device_rank_normalize(view, center=None):
     """``z_scale`` of every (ensemble, parameter) of a ChainView, taken where the chain lies
     (bisip_chain_rank_normalize_dev): the derived ChainView of a new tensor ``(n, n_ensembles * Wp, ndim)``.  The ensembles
-    go in passes whose gathered columns stay under ``RANK_PASS_BYTES`` (one sort takes fewer than 2^31 values)."""
+    go in passes whose gathered columns stay under ``RANK_PASS_BYTES`` (one sort takes fewer than 2^31 values).
+    ``center (n_ensembles, ndim)``: ``z_scale(abs(x - center))`` instead, folded where the values are read
+    (bisip_chain_rank_normalize_folded_dev; bisip_amd.diagnostics)."""
     import torch
     from . import _hip
     n, E, Wp, ndim = view.n, view.n_ensembles, view.walkers_per_ensemble, view.ndim
+    if center is not None:
+        center = np.ascontiguousarray(center, dtype=np.float64)
+        if center.shape != (E, ndim):
+            raise ValueError(f'center must have shape ({E}, {ndim}), got {center.shape}')
+        center = view.upload(center)
     z = view.empty((n, E * Wp, ndim), torch.float64)
     G = int(min(E, max(1, RANK_PASS_BYTES // (n * Wp * ndim * 8))))
     if _hip.chain_rank_normalize_workspace(n, G, Wp, ndim) <= 0:
@@ -283,8 +290,13 @@ def device_rank_normalize(view):
         nbytes = _hip.chain_rank_normalize_workspace(n, k, Wp, ndim)
         work = view.empty((nbytes,), torch.uint8)
         part = z if k == E else view.empty((n, k * Wp, ndim), torch.float64)
-        _hip.chain_rank_normalize_dev(view.ptr + 8 * g0 * Wp * ndim, n, view.stride, k, Wp, ndim, part.data_ptr(),
-                                      work.data_ptr(), nbytes, view.stream)
+        if center is None:
+            _hip.chain_rank_normalize_dev(view.ptr + 8 * g0 * Wp * ndim, n, view.stride, k, Wp, ndim, part.data_ptr(),
+                                          work.data_ptr(), nbytes, view.stream)
+        else:
+            _hip.chain_rank_normalize_folded_dev(view.ptr + 8 * g0 * Wp * ndim, n, view.stride, k, Wp, ndim,
+                                                 center.data_ptr() + 8 * g0 * ndim, part.data_ptr(), work.data_ptr(), nbytes,
+                                                 view.stream)
         if part is not z:                                        # (same stream: ordered after the kernel)
             z[:, g0 * Wp:(g0 + k) * Wp].copy_(part)
         view.synchronize()

@@ -3,7 +3,7 @@
 ``DeviceChainSummaries`` is the part of ``DeviceEnsembleSampler`` that has nothing to do with sampling: it finds the
 used samples of the stored chain (or log-probability) on the device as a ChainView and hands that to the ``device_*``
 function of the family asked for (bisip_amd.chainview, .autocorr, .histogram, .trace, .convergence, .covariance,
-.interval, .ess, .decomposition, .response).
+.interval, .ess, .diagnostics, .decomposition, .response).
 ``device_model_percentiles`` also needs the model: forward over the samples, then the order statistics of each response.
 """
 
@@ -15,6 +15,7 @@ from .autocorr import check_c, check_tol, device_integrated_time
 from .chainview import ChainView, _merge_device_parts, device_moments, device_percentiles, used_range
 from .convergence import device_rhat
 from .covariance import corr_from_cov, device_best_sample, device_cov
+from .diagnostics import device_ess_sd, device_mcse_sd, device_rank_rhat, device_summary
 from .ess import device_ess, device_mcse_mean
 from .fitquality import device_fit_quality
 from .interval import device_hdi
@@ -208,6 +209,33 @@ class DeviceChainSummaries:
         """The Monte-Carlo standard error of every posterior mean, ``(n_ensembles, ndim)``: param_moments' standard
         deviation times ``sqrt(N / (N - 1))`` over the square root of the 'mean' effective sample size."""
         return device_mcse_mean(self.used_samples_dev(discard, thin))
+
+    def param_rank_rhat(self, discard=0, thin=1, split=True, parts=False):
+        """The rank-normalised folded R-hat (bisip_amd.diagnostics.rank_rhat) of every parameter of every ensemble over
+        its walkers' series of ``get_chain(discard, thin)``: ``(n_ensembles, ndim)``, with ``parts=True`` ``(rank_rhat,
+        bulk, folded)``, taken on the device (bisip_chain_rank_normalize_dev and ..._folded_dev, bisip_chain_rhat_dev)
+        from the chain where it lies (``chain_on_device``), else from an upload of the used samples only."""
+        return device_rank_rhat(self.used_samples_dev(discard, thin), split, parts)
+
+    def log_prob_rank_rhat(self, discard=0, thin=1, split=True):
+        """The rank-normalised folded R-hat of every ensemble's stored log-probability, ``(n_ensembles,)``."""
+        return device_rank_rhat(self.log_prob_samples_dev(discard, thin), split)[:, 0]
+
+    def param_ess_sd(self, discard=0, thin=1, split=True):
+        """The effective sample size of the squared distances from the posterior mean (diagnostics.ess_sd), ``(n_ensembles,
+        ndim)``: bisip_chain_ess_squares_dev about param_moments' mean."""
+        return device_ess_sd(self.used_samples_dev(discard, thin), split)
+
+    def param_mcse_sd(self, discard=0, thin=1, split=True):
+        """The Monte-Carlo standard error of every posterior standard deviation (diagnostics.mcse_sd), ``(n_ensembles,
+        ndim)``: bisip_chain_central_moments_dev and param_ess_sd."""
+        return device_mcse_sd(self.used_samples_dev(discard, thin), split)
+
+    def param_summary(self, mass=0.95, discard=0, thin=1, split=True):
+        """The posterior table (diagnostics.summary) of every ensemble: a dict of ``(n_ensembles, ndim)`` arrays ``mean``,
+        ``sd`` (ddof = 1), ``hdi_lo``, ``hdi_hi``, ``mcse_mean``, ``mcse_sd``, ``ess_bulk``, ``ess_tail``, ``r_hat``, with
+        one plain and one folded rank pass for all of them."""
+        return device_summary(self.used_samples_dev(discard, thin), mass, split)
 
     def param_cov(self, discard=0, thin=1):
         """``np.cov`` (ddof = 1) of every ensemble's used samples flattened over its walkers -- of ``get_chain(discard,

@@ -14,6 +14,7 @@ import numpy as np
 
 from .chainview import used_range
 from .covariance import ModelCovariance
+from .diagnostics import ModelDiagnostics
 from .ess import ModelEss
 from .fitquality import ModelFitQuality
 from .interval import ModelIntervals
@@ -185,11 +186,12 @@ def refuse_discard_of_a_chain(kwargs):
                          'thin keywords to parse the full chain. Do not pass both.')
 
 
-class utils(ModelCovariance, ModelIntervals, ModelEss, ModelResponse, ModelFitQuality, ModelLoo):
+class utils(ModelCovariance, ModelIntervals, ModelEss, ModelDiagnostics, ModelResponse, ModelFitQuality, ModelLoo):
     """Mixin with the reference's utility methods (src/bisip/utils.py:15); the posterior covariance, correlation and best
     sample come from bisip_amd.covariance.ModelCovariance, the highest-density intervals from
-    bisip_amd.interval.ModelIntervals, the effective sample sizes from bisip_amd.ess.ModelEss, the amplitude / phase
-    bands and the moments of the model response from bisip_amd.response.ModelResponse, WAIC, DIC and the per-point misfit
+    bisip_amd.interval.ModelIntervals, the effective sample sizes from bisip_amd.ess.ModelEss, the rank-normalised R-hat
+    and the posterior table from bisip_amd.diagnostics.ModelDiagnostics, the amplitude / phase bands and the moments of
+    the model response from bisip_amd.response.ModelResponse, WAIC, DIC and the per-point misfit
     from bisip_amd.fitquality.ModelFitQuality, PSIS-LOO and the Pareto k of every point from bisip_amd.loo.ModelLoo."""
 
     def load_data(self, filename, headers=1, ph_units='mrad'):
@@ -354,7 +356,8 @@ class utils(ModelCovariance, ModelIntervals, ModelEss, ModelResponse, ModelFitQu
         (bisip_amd.convergence): ``sqrt((L - 1) / L + Bn / Wn)`` with ``Wn`` the mean of the walkers' variances and
         ``Bn`` the variance of their means; ``split=True`` cuts every walker's series into halves first, which also shows
         drift and works from four used samples up.  Walkers of an ensemble sampler are not independent chains: this is a
-        screening number used beside ``get_autocorr_time``, not a replacement for it.  ``chain``: an unflattened chain,
+        screening number used beside ``get_autocorr_time``, not a replacement for it.  get_rank_rhat is the R-hat that
+        also sees walkers of different scale and a shifted walker under heavy tails.  ``chain``: an unflattened chain,
         else ``discard`` / ``thin`` as for ``get_chain``.  A fit with the device sampler is reduced on the GPU
         (``chain='device'``: where the chain lies), an explicit ``chain`` or a host sampler's in NumPy."""
         from . import convergence as cv

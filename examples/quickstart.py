@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's README quickstart (README.md:38-50 of clberube/BISIP) on the MI355X path:
-the only change is the import.  Prints posterior means / standard deviations and a few
-model-space percentiles."""
+the only change is the import.  Prints posterior means / standard deviations, a few
+model-space percentiles and the posterior table."""
 import os
 import sys
 
@@ -23,3 +23,4 @@ print('std        ', np.round(model.get_param_std(chain), 5))
 lo, med, hi = model.get_model_percentile([2.5, 50, 97.5], chain)          # (3, 2, N): batched forward on the GPU
 print('|Z| median ', np.round(np.hypot(med[0], med[1])[:5], 4), '...')
 print('acceptance ', round(float(model.sampler.acceptance_fraction.mean()), 3), 'path', model.sampler.last_path)
+model.print_summary(discard=500)                              # the posterior table: mean, sd, HDI, MCSE, ESS, rank-normalised R-hat

@@ -344,6 +344,22 @@ int bisip_chain_moments_dev(const double *d_chain, int64_t n_samples, int64_t sa
                             int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim,
                             double *d_mean, double *d_std, double *d_work, void *stream);
 
+/* The second and fourth moments of every (ensemble, parameter) about a given centre: d_m2 and d_m4 (n_ensembles, ndim), the
+ * means of (x - c)^2 and (x - c)^4 over the N = n_samples * walkers_per_ensemble values, c = d_center[e, q] (n_ensembles,
+ * ndim) -- what the Monte-Carlo error of the standard deviation is made of (bisip_amd/diagnostics.py: mcse_sd).  Chain
+ * layout, d_chain / sample_stride conventions and the order as for pass 1 of bisip_chain_moments_dev: its splits, lanes,
+ * four accumulators per lane and per moment, (a0 + a1) + (a2 + a3), lanes and then splits in ascending order onto 0.0.
+ * Per value: d = x - c (one rounding), q = d * d (one rounding), acc2 = fma(d, d, acc2), acc4 = fma(q, q, acc4); m = sum /
+ * count, count = double(n) * double(Wp).  IEEE throughout: a centre or a value that is not finite makes both moments of
+ * its (ensemble, parameter) NaN or +inf, nothing else changes.
+ * d_work: bisip_chain_central_moments_workspace() DOUBLES, as bisip_chain_moments_workspace counts, times two.
+ * BISIP_EINVAL and nothing written for a null pointer, a shape out of range or sample_stride < E * Wp * ndim.  No atomics:
+ * the same bits on every call (diagnostics.ordered_central_moments gives them in NumPy).  Asynchronous on stream. */
+int64_t bisip_chain_central_moments_workspace(int64_t n_samples, int64_t n_ensembles, int ndim);
+int bisip_chain_central_moments_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride,
+                                    int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim,
+                                    const double *d_center, double *d_m2, double *d_m4, double *d_work, void *stream);
+
 /* Percentiles of every parameter, per ensemble, of a chain resident in device memory -- the
  * device form of get_param_percentile (src/bisip/utils.py:37-53: np.percentile(chain, p,
  * axis=0), linear interpolation; the reference's default p is [2.5, 50, 97.5]).  Chain layout,
@@ -614,6 +630,16 @@ int bisip_chain_ess_dev(const double *d_chain, int64_t n_samples, int64_t sample
                         int64_t walkers_per_ensemble, int ndim, int splits, const double *d_threshold, int n_threshold,
                         double *d_ess, void *d_work, int64_t work_bytes, void *stream);
 
+/* The same of the squares about a centre: bisip_chain_ess_dev on the series (x - c) * (x - c), c = d_center[e, q]
+ * (n_ensembles, ndim), taken on load as the indicators are -- one subtraction and one multiplication, each rounded -- so
+ * the bits are those of bisip_chain_ess_dev on a stored chain of these squares.  d_ess (n_ensembles, ndim): the effective
+ * sample size that the standard deviation's Monte-Carlo error is taken with (bisip_amd/diagnostics.py: ess_sd).  A
+ * centre that is NaN gives NaN (as does one that is infinite: every square is).  Everything else, the checks and the
+ * work included, as for bisip_chain_ess_dev without thresholds; d_work: bisip_chain_ess_workspace(..., n_threshold = 0). */
+int bisip_chain_ess_squares_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+                                int64_t walkers_per_ensemble, int ndim, int splits, const double *d_center, double *d_ess,
+                                void *d_work, int64_t work_bytes, void *stream);
+
 /* Rank-normalisation of a chain resident in device memory, what the bulk effective sample size is taken of
  * (bisip_amd/ess.py: z_scale).  Chain layout, d_chain / sample_stride conventions as above.  Per (ensemble, parameter)
  * the N = n_samples * walkers_per_ensemble values are ranked from 1, ties sharing the mean of their ranks (-0.0 and 0.0
@@ -630,6 +656,16 @@ int64_t bisip_chain_rank_normalize_workspace(int64_t n_samples, int64_t n_ensemb
 int bisip_chain_rank_normalize_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
                                    int64_t walkers_per_ensemble, int ndim, double *d_z, void *d_work, int64_t work_bytes,
                                    void *stream);
+
+/* The same of the folded values fabs(x - c), c = d_center[e, q] (n_ensembles, ndim; the median, for the folded R-hat of
+ * bisip_amd/diagnostics.py: rank_rhat).  The fold is one IEEE subtraction and fabs, applied where a value is read: on the
+ * gathered columns, in place, before the sort, and on the element before its two searches -- no chain-sized intermediate,
+ * and the bits of bisip_chain_rank_normalize_dev on a stored chain of the folded values.  Same sort, same searches, same
+ * PPND16.  A centre or a value that is not finite makes every z of its (ensemble, parameter) NaN and no other.
+ * d_work: bisip_chain_rank_normalize_workspace() of the same shape.  The checks as for bisip_chain_rank_normalize_dev. */
+int bisip_chain_rank_normalize_folded_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride,
+                                          int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim,
+                                          const double *d_center, double *d_z, void *d_work, int64_t work_bytes, void *stream);
 
 /* np.percentile(rows, p, axis=0) for a device-resident (n_rows, n_cols) array (linear rule):
  * d_out (n_percentiles, n_cols).  Workspace in BYTES (0: more than 2^31 values). */
