@@ -198,6 +198,15 @@ SYMBOLS = {
     'bisip_loo_columns_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_int64, ctypes.c_void_p]),
+    'bisip_bridge_logg_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 5),
+    'bisip_bridge_draw_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int,
+                                             ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p]),
+    'bisip_bridge_scale_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.c_int64] + [ctypes.c_void_p] * 5),
+    'bisip_bridge_iterate_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                                ctypes.c_void_p, ctypes.c_double, ctypes.c_int64] + [ctypes.c_void_p] * 5),
     'bisip_ctx_reduced_check': (ctypes.c_int, [ctypes.c_void_p, _dp, ctypes.c_int64, _dp, _dp]),
     'bisip_read_tables': (ctypes.c_int, [ctypes.POINTER(ctypes.c_char_p), ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
@@ -1215,6 +1224,46 @@ def loo_columns_dev(d_q_ptr, n, columns, tail_len, d_elpd_rel_ptr, d_khat_ptr, d
     _check(load_library().bisip_loo_columns_dev(d_q_ptr or None, int(n), int(columns), int(tail_len), d_elpd_rel_ptr or None,
                                                 d_khat_ptr or None, d_sigma_ptr or None, d_ntail_ptr or None,
                                                 d_work_ptr or None, int(work_bytes), stream))
+
+
+def bridge_logg_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, d_logp_ptr, logp_stride,
+                    d_mean_ptr, d_chol_ptr, d_const_ptr, d_l_ptr, stream=0):
+    """Bridge sampling, step 1: ``l = logp - log_g`` of every stored row into d_l ``(n_ensembles, n_samples *
+    walkers_per_ensemble)``; the proposal is d_mean ``(n_ensembles, ndim)``, d_chol ``(n_ensembles, ndim, ndim)`` lower and
+    d_const ``(n_ensembles,)`` (bisip_amd.evidence).  Device pointers (ints), asynchronous on ``stream``."""
+    _check(load_library().bisip_bridge_logg_dev(d_chain_ptr or None, int(n_samples), int(sample_stride), int(n_ensembles),
+                                                int(walkers_per_ensemble), int(ndim), d_logp_ptr or None, int(logp_stride),
+                                                d_mean_ptr or None, d_chol_ptr or None, d_const_ptr or None, d_l_ptr or None,
+                                                stream))
+
+
+def bridge_draw_dev(d_mean_ptr, d_chol_ptr, d_const_ptr, n_ensembles, ndim, n_draws, seed, first_draw, first_ensemble,
+                    d_theta_ptr, d_logg_ptr, stream=0):
+    """Bridge sampling, step 2: draws ``first_draw ... first_draw + n_draws - 1`` of every ensemble's proposal into d_theta
+    ``(n_ensembles * n_draws, ndim)`` and their ``log_g`` into d_logg ``(n_ensembles * n_draws,)``; ensemble ``e`` draws from
+    the Philox stream of ``first_ensemble + e``.  Device pointers (ints), asynchronous on ``stream``."""
+    _check(load_library().bisip_bridge_draw_dev(d_mean_ptr or None, d_chol_ptr or None, d_const_ptr or None, int(n_ensembles),
+                                                int(ndim), int(n_draws), int(seed) & 0xffffffffffffffff, int(first_draw),
+                                                int(first_ensemble), d_theta_ptr or None, d_logg_ptr or None, stream))
+
+
+def bridge_scale_dev(d_l1_ptr, n1, d_logp2_ptr, d_logg2_ptr, n2, n_ensembles, d_lstar_ptr, d_l2_ptr, d_a1_ptr, d_a2_ptr,
+                     stream=0):
+    """Bridge sampling, step 3: ``a1 = exp(-(l2 - lstar))`` ``(n_ensembles, n2)`` with ``l2 = logp2 - logg2`` (into d_l2, 0 /
+    None or one of its two inputs) and ``a2 = exp(l1 - lstar)`` ``(n_ensembles, n1)``.  Device pointers (ints)."""
+    _check(load_library().bisip_bridge_scale_dev(d_l1_ptr or None, int(n1), d_logp2_ptr or None, d_logg2_ptr or None, int(n2),
+                                                 int(n_ensembles), d_lstar_ptr or None, d_l2_ptr or None, d_a1_ptr or None,
+                                                 d_a2_ptr or None, stream))
+
+
+def bridge_iterate_dev(d_a1_ptr, n2, d_a2_ptr, n1, n_ensembles, d_s1_ptr, tol, maxiter, d_r_ptr, d_iterations_ptr,
+                       d_moments_ptr, d_f2_ptr=0, stream=0):
+    """Bridge sampling, step 4: the iteration of every ensemble on the device: d_r ``(n_ensembles,)`` the final ``r``,
+    d_iterations ``(n_ensembles,)`` int64, d_moments ``(n_ensembles, 4)``, d_f2 ``(n_ensembles, n1)`` or 0 / None.  Device
+    pointers (ints), asynchronous on ``stream``."""
+    _check(load_library().bisip_bridge_iterate_dev(d_a1_ptr or None, int(n2), d_a2_ptr or None, int(n1), int(n_ensembles),
+                                                   d_s1_ptr or None, float(tol), int(maxiter), d_r_ptr or None,
+                                                   d_iterations_ptr or None, d_moments_ptr or None, d_f2_ptr or None, stream))
 
 
 def grouped_percentiles_workspace(n_groups, n_rows, n_cols, n_percentiles):

@@ -18,6 +18,7 @@ from .fitquality import BatchFitQuality
 from .interval import BatchIntervals
 from .dist import shard_range
 from .loo import BatchLoo
+from .evidence import BatchEvidence
 from .response import BatchResponse
 from .sampler import DeviceEnsembleSampler
 from .summaries import device_model_percentiles
@@ -54,7 +55,7 @@ def default_params(model, n_modes=1, poly_deg=5):
 
 
 class SpectraBatch(BatchCovariance, BatchIntervals, BatchEss, BatchDiagnostics, BatchResponse, BatchFitQuality, BatchLoo,
-                   decomposition.BatchRelaxation):
+                   BatchEvidence, decomposition.BatchRelaxation):
     """E spectra inverted together with the same model class.
 
     Args:

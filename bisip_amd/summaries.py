@@ -244,6 +244,16 @@ class DeviceChainSummaries:
         only."""
         return device_cov(self.used_samples_dev(discard, thin))
 
+    def evidence(self, discard=0, thin=1, **kwargs):
+        """The bridge-sampling estimate of every ensemble's log marginal likelihood (bisip_amd.evidence.device_evidence, whose
+        keywords ``kwargs`` are): the first half of ``get_chain(discard, thin)`` fits a normal proposal, the second half with
+        its stored log-probability and draws of the proposal enter the estimator, all on the device (bisip_bridge_*_dev,
+        bisip_logprob_dev) from the chain where it lies (``chain_on_device``), else from an upload of the used samples only.
+        A dict of ``(n_ensembles,)`` arrays ``log_ml``, ``se``, ``iterations``, ..."""
+        from .evidence import device_evidence
+        return device_evidence(self.used_samples_dev(discard, thin), self.log_prob_samples_dev(discard, thin),
+                               self.backend.ctx, **kwargs)
+
     def param_corr(self, discard=0, thin=1):
         """``np.corrcoef`` of the same samples, ``(n_ensembles, ndim, ndim)``: the device's covariance divided on the host
         (covariance.corr_from_cov); NaN where a parameter does not vary."""

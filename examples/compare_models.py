@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Which model does the spectrum support: Pelton Cole-Cole with one mode and with two, fitted to the same spectrum and
-ranked by WAIC and by PSIS-LOO, and where the better one still misses the data.  The chains stay on the GPU; the sums over
-them (bisip_fit_quality_dev) and the Pareto-smoothed tails of every data point (bisip_loo_columns_dev) are taken there."""
+ranked by WAIC, by PSIS-LOO and by their marginal likelihood (bridge sampling), and where the better one still misses the
+data.  The chains stay on the GPU; the sums over them (bisip_fit_quality_dev), the Pareto-smoothed tails of every data point
+(bisip_loo_columns_dev) and the bridge-sampling iteration (bisip_bridge_*_dev) are taken there."""
 import os
 import sys
 
@@ -10,11 +11,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))) 
 import numpy as np
 
 from bisip_amd import DataFiles, PeltonColeCole
+from bisip_amd.evidence import compare_evidence
 from bisip_amd.fitquality import compare_waic
 from bisip_amd.loo import compare_loo
 
 filepath = DataFiles()['SIP-K389174']                         # two bumps in its imaginary part (docs/tutorials/pelton.ipynb)
-results, loos, models = {}, {}, {}
+results, loos, evidences, models = {}, {}, {}, {}
 for n_modes in (1, 2):
     np.random.seed(42)
     model = PeltonColeCole(filepath, nwalkers=64, nsteps=2000, n_modes=n_modes)
@@ -23,6 +25,7 @@ for n_modes in (1, 2):
     model.fit(chain='device')
     name = f'{n_modes} mode' + 's' * (n_modes > 1)
     results[name], loos[name], models[name] = model.get_waic(discard=1000), model.get_loo(discard=1000), model
+    evidences[name] = model.get_evidence(discard=1000)          # the log marginal likelihood by bridge sampling
     dic = model.get_dic(discard=1000)
     print(f'{name}: DIC {dic["dic"]:.1f}, p_D {dic["p_d"]:.1f}; {results[name]["n_high"]} points with p_waic > 0.4')
 
@@ -34,6 +37,11 @@ for row in compare_waic(results):                             # the best model f
 print('model       elpd_loo   p_loo   d_elpd    d_se  n_bad')
 for row in compare_loo(loos):
     print(f'{row["name"]:<10} {row["elpd_loo"]:9.1f} {row["p_loo"]:7.1f} {row["d_elpd"]:8.1f} {row["d_se"]:7.1f} {row["n_bad"]:6d}')
+
+# the evidence itself: Bayes factors against the best model and posterior model probabilities under equal prior odds
+print('model      log_evidence   log_bf    prob      se')
+for row in compare_evidence(evidences):
+    print(f'{row["name"]:<10} {row["log_evidence"]:12.2f} {row["log_bf"]:8.2f} {row["prob"]:7.3f} {row["se"]:7.2f}')
 
 best = compare_waic(results)[0]['name']
 misfit = models[best].get_pointwise_misfit(discard=1000)      # (2, N): near 1, the point is fitted to its error bar

@@ -794,6 +794,67 @@ int64_t bisip_loo_columns_workspace(int64_t n, int64_t columns, int64_t tail_len
 int bisip_loo_columns_dev(const double *d_q, int64_t n, int64_t columns, int64_t tail_len, double *d_elpd_rel, double *d_khat,
                           double *d_sigma, int64_t *d_ntail, void *d_work, int64_t work_bytes, void *stream);
 
+/* BRIDGE SAMPLING: the log marginal likelihood of every ensemble of a chain resident in device memory (Meng & Wong 1996 with a
+ * multivariate-normal proposal, arranged as Gronau et al. 2017; bisip_amd/evidence.py holds the definitions: bridge_terms,
+ * bridge_iterate, bridge_evidence).  Four steps, no context; the log-probability of the proposal's draws between the second
+ * and the third is bisip_logprob_dev's.  The proposal of ensemble e: d_mean (n_ensembles, ndim), d_chol (n_ensembles, ndim,
+ * ndim) the LOWER Cholesky factor L, row-major (the upper triangle is never read), d_const (n_ensembles) = c = sum_j log L_jj +
+ * (ndim / 2) log(2 pi), taken by the caller.  log_g(x) = -0.5 sum_j z_j^2 - c with L z = x - mu.
+ * All four: no workspace, no floating-point atomics (the same bits on every call), 64-bit offsets, asynchronous on stream,
+ * no host synchronisation; BISIP_EINVAL and nothing written for a null pointer (d_f2, d_l2 excepted) or a shape out of range
+ * (ndim outside 1 ... BISIP_MAX_NDIM, a count < 1, a stride smaller than one sample).
+ *
+ * Step 1: d_l (n_ensembles, N), N = n_samples * walkers_per_ensemble, column r = k * walkers_per_ensemble + w of ensemble e:
+ * l = logp - log_g(x) of walker w of the ensemble in used sample k.  Chain layout, d_chain / sample_stride as for
+ * bisip_chain_cov_dev; d_logp / logp_stride as for bisip_chain_best_sample_dev.  Order of every operation, each rounded once:
+ * d_j = x_j - mu_j; acc = d_j, acc = fma(-L_jk, z_k, acc) for k = 0 ... j - 1 ascending, z_j = acc / L_jj; m = fma(z_j, z_j,
+ * m) for j ascending from 0.0; log_g = fma(-0.5, m, -c); l = logp - log_g.  evidence.ordered_logg gives the same bits in
+ * NumPy.  A logp or a parameter that is -inf, +inf or NaN propagates by IEEE to its own l and no other.  Rows are cut into
+ * segments as bisip_chain_cov_dev cuts them and a tile of 256 rows is staged through LDS in whole lines; L and mu are read
+ * once per workgroup; one lane takes one row.  No sum crosses a row: the cut changes no bit. */
+int bisip_bridge_logg_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+                          int64_t walkers_per_ensemble, int ndim, const double *d_logp, int64_t logp_stride,
+                          const double *d_mean, const double *d_chol, const double *d_const, double *d_l, void *stream);
+
+/* Step 2: n_draws draws of every ensemble's proposal.  d_theta (n_ensembles * n_draws, ndim), rows [e * n_draws, (e + 1) *
+ * n_draws) of ensemble e -- the row layout bisip_logprob_dev takes of a batch context -- and d_logg (n_ensembles * n_draws)
+ * their log_g.  Draw i (numbered first_draw + i, 64 bits) of ensemble e takes its normal pair p = 0 ... ceil(ndim / 2) - 1 from
+ * philox4x32_10(counter = (lo32(first_draw + i), hi32(first_draw + i), first_ensemble + e, 0x42520000 | p), key = (lo32(seed),
+ * hi32(seed))) = (v0, v1, v2, v3): u0 = u53(v0, v1), u1 = u53(v2, v3) (53-bit uniforms in [0, 1)), rad = sqrt(-2 log(1 - u0)),
+ * (z_2p, z_2p+1) = (rad * cospi(2 u1), rad * sinpi(2 u1)).  The samplers' streams keep counter word 3 in {0, 1, 2}: the domains
+ * cannot meet.  theta_j = mu_j, theta_j = fma(L_jk, z_k, theta_j) for k = 0 ... j ascending; m = fma(z_j, z_j, m) for j
+ * ascending from 0.0, log_g = fma(-0.5, m, -c).  A draw is a function of (seed, first_ensemble + e, first_draw + i) alone:
+ * a call for draws [0, n) equals, bit for bit, calls for [0, k) and [k, n).  The integers are exact; log, sqrt and sincospi are
+ * the device library's.  first_ensemble + n_ensembles <= 2^32, n_draws <= 2^40.  One lane per draw. */
+int bisip_bridge_draw_dev(const double *d_mean, const double *d_chol, const double *d_const, int64_t n_ensembles, int ndim,
+                          int64_t n_draws, uint64_t seed, uint64_t first_draw, int64_t first_ensemble, double *d_theta,
+                          double *d_logg, void *stream);
+
+/* Step 3, elementwise: with l2 = d_logp2 - d_logg2 (n_ensembles, n2) (the log-probability of the draws, -inf outside the prior
+ * box, and their log_g) and d_l1 (n_ensembles, n1) of step 1,
+ *   d_a1 (n_ensembles, n2) = exp(-(l2 - lstar_e)),   d_a2 (n_ensembles, n1) = exp(l1 - lstar_e),
+ * lstar = d_lstar (n_ensembles).  d_l2 (n_ensembles, n2) takes l2 itself; it may be NULL and may be d_logp2 or d_logg2.  Each
+ * subtraction and the negation are rounded on their own; exp is the device library's.  l2 = -inf gives a1 = +inf exactly; a NaN
+ * stays a NaN. */
+int bisip_bridge_scale_dev(const double *d_l1, int64_t n1, const double *d_logp2, const double *d_logg2, int64_t n2,
+                           int64_t n_ensembles, const double *d_lstar, double *d_l2, double *d_a1, double *d_a2, void *stream);
+
+/* Step 4: the iteration.  s1 = d_s1[e], s2 = 1 - s1; from r = 1:
+ *   r' = (sum_i f1_i / n2) / (sum_j f2_j / n1),  f1_i = 1 / (s1 + (s2 * r) * a1_i),  f2_j = 1 / fma(s1, a2_j, s2 * r),
+ * until |r' - r| <= tol * r' or maxiter passes (>= 1) are done.  A pass whose r' is not a positive finite number (a sum that is
+ * not finite, a denominator of 0, every a1 = +inf) ends the ensemble there with r = NaN.  a1 = +inf and a2 = +inf contribute
+ * exactly 0.  d_r (n_ensembles): the final r -- log_ml = log(r) + lstar is the caller's, the kernel takes no log;
+ * d_iterations (n_ensembles, int64): passes done; d_moments (n_ensembles, 4): mean and population variance of f1, then of f2,
+ * at the final r; d_f2 (n_ensembles, n1) or NULL: f2 at the final r.
+ * Order.  One workgroup of 256 threads per ensemble loops on the device.  Term i of a sum goes to slot i mod 256; a slot adds
+ * its terms in ascending order from 0.0; the slots are added pairwise within each run of 64, 32, 16, ..., 1 apart; the four runs
+ * in ascending order; a mean is sum / double(count).  The variances are a second pass at the final r: d = f - mean, acc =
+ * fma(d, d, acc) per slot, the same tree, / double(count).  Only + - * / and fma: evidence.ordered_iterate gives the same bits,
+ * the pass count included. */
+int bisip_bridge_iterate_dev(const double *d_a1, int64_t n2, const double *d_a2, int64_t n1, int64_t n_ensembles,
+                             const double *d_s1, double tol, int64_t maxiter, double *d_r, int64_t *d_iterations,
+                             double *d_moments, double *d_f2, void *stream);
+
 /* Host: the stretch move's random stream in numpy.random.RandomState order for n_steps
  * iterations of a W-walker ensemble (the contract is bisip_amd/sampler.py:draw_step).
  * mt_key[624] / *mt_pos are RandomState.get_state()[1:3], advanced in place exactly as
