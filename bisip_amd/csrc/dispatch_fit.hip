@@ -241,25 +241,7 @@ int launch_fit(const FqArgs &a, unsigned blocks, hipStream_t st)
 
 int dispatch_fit(const bisip_ctx *c, const FqArgs &a, unsigned blocks, hipStream_t st)
 {
-    switch (c->model_id) {
-    case BISIP_MODEL_POLYDECOMP:
-        switch (c->P) {
-#define X(p) case p: return launch_fit<PDCollapsed<p>>(a, blocks, st);
-            PD_CASES(X)
-#undef X
-        }
-        break;
-    case BISIP_MODEL_COLECOLE:
-        switch (c->D) {
-#define X(d) case d: return launch_fit<ColeCole<d>>(a, blocks, st);
-            CC_CASES(X)
-#undef X
-        }
-        break;
-    case BISIP_MODEL_DIAS2000: return launch_fit<Dias>(a, blocks, st);
-    case BISIP_MODEL_SHIN2015: return launch_fit<Shin>(a, blocks, st);
-    }
-    return fail(BISIP_EUNSUPPORTED, "no fit-quality kernel for this model shape");
+    return with_model(c, "fit-quality", [&](auto m) { return launch_fit<typename decltype(m)::type>(a, blocks, st); });
 }
 
 // bytes of the segments' states and the shifts; 0 with one segment, -1 when the grid does not exist

@@ -56,11 +56,10 @@ int launch_forward_columns(const bisip_ctx *c, const double *theta, int64_t W, d
     return BISIP_OK;
 }
 
+// a batch whose 64-walker blocks straddle spectra: one thread per (row, frequency)
 template <class M>
 int launch_forward_batch(const bisip_ctx *c, const double *theta, int64_t W, double *Z, hipStream_t st)
 {
-    // 64-walker blocks never straddle two spectra: the tiled / whole-row kernels apply
-    if ((W / c->E) % 64 == 0) return launch_forward<M>(c, theta, W, Z, st);
     const BatchArgs a = make_batch_args(c, theta, Z, W);
     const long long total = (long long)W * c->N;
     hipLaunchKernelGGL((k_forward_batch<M>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a);
@@ -70,25 +69,7 @@ int launch_forward_batch(const bisip_ctx *c, const double *theta, int64_t W, dou
 
 int dispatch_forward_batch(const bisip_ctx *c, const double *theta, int64_t W, double *Z, hipStream_t st)
 {
-    switch (c->model_id) {
-    case BISIP_MODEL_POLYDECOMP:
-        switch (c->P) {
-#define X(p) case p: return launch_forward_batch<PDCollapsed<p>>(c, theta, W, Z, st);
-            X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10)
-#undef X
-        }
-        break;
-    case BISIP_MODEL_COLECOLE:
-        switch (c->D) {
-#define X(d) case d: return launch_forward_batch<ColeCole<d>>(c, theta, W, Z, st);
-            X(1) X(2) X(3) X(4) X(5)
-#undef X
-        }
-        break;
-    case BISIP_MODEL_DIAS2000: return launch_forward_batch<Dias>(c, theta, W, Z, st);
-    case BISIP_MODEL_SHIN2015: return launch_forward_batch<Shin>(c, theta, W, Z, st);
-    }
-    return fail(BISIP_EUNSUPPORTED, "no batch forward kernel for this model shape");
+    return with_model(c, "batch forward", [&](auto m) { return launch_forward_batch<typename decltype(m)::type>(c, theta, W, Z, st); });
 }
 
 }  // namespace
@@ -105,25 +86,7 @@ int dispatch_forward_columns(const bisip_ctx *c, const double *theta, int64_t W,
     if (W % count) return fail(BISIP_EINVAL, "W=%lld rows do not divide over %lld spectra", (long long)W, count);
     if ((W + 63) / 64 > 0x7fffffffLL) return fail(BISIP_EINVAL, "W=%lld exceeds the launch grid limit", (long long)W);
     if (((uintptr_t)theta % 8) || ((uintptr_t)cols % 8)) return fail(BISIP_EINVAL, "buffers must be 8-byte aligned");
-    switch (c->model_id) {
-    case BISIP_MODEL_POLYDECOMP:
-        switch (c->P) {
-#define X(p) case p: return launch_forward_columns<PDCollapsed<p>>(c, theta, W, cols, st, spectrum, count, kind);
-            PD_CASES(X)
-#undef X
-        }
-        break;
-    case BISIP_MODEL_COLECOLE:
-        switch (c->D) {
-#define X(d) case d: return launch_forward_columns<ColeCole<d>>(c, theta, W, cols, st, spectrum, count, kind);
-            CC_CASES(X)
-#undef X
-        }
-        break;
-    case BISIP_MODEL_DIAS2000: return launch_forward_columns<Dias>(c, theta, W, cols, st, spectrum, count, kind);
-    case BISIP_MODEL_SHIN2015: return launch_forward_columns<Shin>(c, theta, W, cols, st, spectrum, count, kind);
-    }
-    return fail(BISIP_EUNSUPPORTED, "no forward kernel for this model shape");
+    return with_model(c, "forward-columns", [&](auto m) { return launch_forward_columns<typename decltype(m)::type>(c, theta, W, cols, st, spectrum, count, kind); });
 }
 
 int dispatch_forward(const bisip_ctx *c, const double *theta, int64_t W, double *Z, hipStream_t st, long long spectrum,
@@ -138,27 +101,10 @@ int dispatch_forward(const bisip_ctx *c, const double *theta, int64_t W, double 
     if (((uintptr_t)theta % 8) || ((uintptr_t)Z % 8)) return fail(BISIP_EINVAL, "buffers must be 8-byte aligned");
     if (c->E > 1 && spectrum < 0) {
         if (W % c->E) return fail(BISIP_EINVAL, "W=%lld is not a multiple of n_spectra=%d", (long long)W, c->E);
-        return dispatch_forward_batch(c, theta, W, Z, st);
+        if ((W / c->E) % 64) return dispatch_forward_batch(c, theta, W, Z, st);
+        // else 64-walker blocks never straddle two spectra: the tiled / whole-row kernels apply
     }
-    switch (c->model_id) {
-    case BISIP_MODEL_POLYDECOMP:
-        switch (c->P) {
-#define X(p) case p: return launch_forward<PDCollapsed<p>>(c, theta, W, Z, st, spectrum, count);
-            PD_CASES(X)
-#undef X
-        }
-        break;
-    case BISIP_MODEL_COLECOLE:
-        switch (c->D) {
-#define X(d) case d: return launch_forward<ColeCole<d>>(c, theta, W, Z, st, spectrum, count);
-            CC_CASES(X)
-#undef X
-        }
-        break;
-    case BISIP_MODEL_DIAS2000: return launch_forward<Dias>(c, theta, W, Z, st, spectrum, count);
-    case BISIP_MODEL_SHIN2015: return launch_forward<Shin>(c, theta, W, Z, st, spectrum, count);
-    }
-    return fail(BISIP_EUNSUPPORTED, "no forward kernel for this model shape");
+    return with_model(c, "forward", [&](auto m) { return launch_forward<typename decltype(m)::type>(c, theta, W, Z, st, spectrum, count); });
 }
 
 }  // namespace host

@@ -6,13 +6,14 @@ using namespace bisip::host;
 
 namespace {
 
+// theta on a 16-byte boundary: the kernels stage it with vector loads (their VEC argument)
+inline bool aligned16(const double *theta) { return ((uintptr_t)theta % 16) == 0; }
 
 template <class M, int L>
 int launch_logprob_small(const LaunchArgs &a, bool vec, hipStream_t st)
 {
     const unsigned grid = (unsigned)((a.W * L + BLK_SMALL - 1) / BLK_SMALL);
-    if (vec) hipLaunchKernelGGL((k_logprob<M, BLK_SMALL, true, L>), dim3(grid), dim3(BLK_SMALL), 0, st, a);
-    else hipLaunchKernelGGL((k_logprob<M, BLK_SMALL, false, L>), dim3(grid), dim3(BLK_SMALL), 0, st, a);
+    with_flag(vec, [&](auto v) { hipLaunchKernelGGL((k_logprob<M, BLK_SMALL, v, L>), dim3(grid), dim3(BLK_SMALL), 0, st, a); });
     return BISIP_OK;
 }
 
@@ -20,7 +21,7 @@ template <class M>
 int launch_logprob(const bisip_ctx *c, const double *theta, int64_t W, double *out, hipStream_t st)
 {
     const LaunchArgs a = make_args(c, theta, out, W, c->d_cb_lp ? c->d_cb_lp : c->d_cb);
-    const bool vec = ((uintptr_t)theta % 16) == 0;
+    const bool vec = aligned16(theta);
     if (W < SMALL_W) {
         // few walkers: several lanes per walker so the launch still covers the chip
         switch (W <= CoopLimit<M>::value ? lanes_per_walker(W) : 1) {
@@ -30,8 +31,7 @@ int launch_logprob(const bisip_ctx *c, const double *theta, int64_t W, double *o
         }
     } else {
         const unsigned grid = (unsigned)((W + BLK_LARGE - 1) / BLK_LARGE);
-        if (vec) hipLaunchKernelGGL((k_logprob<M, BLK_LARGE, true>), dim3(grid), dim3(BLK_LARGE), 0, st, a);
-        else hipLaunchKernelGGL((k_logprob<M, BLK_LARGE, false>), dim3(grid), dim3(BLK_LARGE), 0, st, a);
+        with_flag(vec, [&](auto v) { hipLaunchKernelGGL((k_logprob<M, BLK_LARGE, v>), dim3(grid), dim3(BLK_LARGE), 0, st, a); });
     }
     HIP_TRY(hipGetLastError());
     return BISIP_OK;
@@ -43,11 +43,11 @@ int launch_collapsed(const bisip_ctx *c, const double *theta, int64_t W, double 
 {
     if (W < SMALL_W) return launch_logprob<PDCollapsed<P>>(c, theta, W, out, st);
     const LaunchArgs a = make_args(c, theta, out, W, c->d_cb_lp);
-    const bool vec = ((uintptr_t)theta % 16) == 0;
     // 256-lane workgroups: 5 % faster than 128 here (benchmarks/micro/collapsed_variants.hip)
     const unsigned grid = (unsigned)((W + 2 * BLK_LARGE - 1) / (2 * BLK_LARGE));
-    if (vec) hipLaunchKernelGGL((k_logprob_x2<PDCollapsed<P>, BLK_LARGE, true>), dim3(grid), dim3(BLK_LARGE), 0, st, a);
-    else hipLaunchKernelGGL((k_logprob_x2<PDCollapsed<P>, BLK_LARGE, false>), dim3(grid), dim3(BLK_LARGE), 0, st, a);
+    with_flag(aligned16(theta), [&](auto v) {
+        hipLaunchKernelGGL((k_logprob_x2<PDCollapsed<P>, BLK_LARGE, v>), dim3(grid), dim3(BLK_LARGE), 0, st, a);
+    });
     HIP_TRY(hipGetLastError());
     return BISIP_OK;
 }
@@ -55,7 +55,7 @@ int launch_collapsed(const bisip_ctx *c, const double *theta, int64_t W, double 
 template <int P, bool COMP>
 int launch_reduced(const bisip_ctx *c, const double *theta, int64_t W, double *out, hipStream_t st)
 {
-    const bool vec = ((uintptr_t)theta % 16) == 0;
+    const bool vec = aligned16(theta);
     if constexpr (COMP && P >= REDUCED_COMP_MEMORY_OPERANDS_FROM) {
         // operands from memory (host.h: REDUCED_COMP_MEMORY_OPERANDS_FROM): the batch kernel, one spectrum
         if (W >= SMALL_W && c->red[1].d_red && c->d_lconst) {
@@ -64,8 +64,9 @@ int launch_reduced(const bisip_ctx *c, const double *theta, int64_t W, double *o
             b.red = c->red[1].d_red;
             b.tier = nullptr;
             const unsigned grid = (unsigned)((W + BLK_LARGE - 1) / BLK_LARGE);
-            if (vec) hipLaunchKernelGGL((k_logprob_batch_reduced_stream<P, BLK_LARGE, true, true>), dim3(grid), dim3(BLK_LARGE), 0, st, b);
-            else hipLaunchKernelGGL((k_logprob_batch_reduced_stream<P, BLK_LARGE, false, true>), dim3(grid), dim3(BLK_LARGE), 0, st, b);
+            with_flag(vec, [&](auto v) {
+                hipLaunchKernelGGL((k_logprob_batch_reduced_stream<P, BLK_LARGE, v, true>), dim3(grid), dim3(BLK_LARGE), 0, st, b);
+            });
             HIP_TRY(hipGetLastError());
             return BISIP_OK;
         }
@@ -75,15 +76,15 @@ int launch_reduced(const bisip_ctx *c, const double *theta, int64_t W, double *o
     fill_reduced<P, COMP>(c, r);
     if (W < SMALL_W) {
         const unsigned grid = (unsigned)((W + BLK_SMALL - 1) / BLK_SMALL);
-        if (vec) hipLaunchKernelGGL((k_logprob_pd_reduced<P, BLK_SMALL, true, COMP>), dim3(grid), dim3(BLK_SMALL), 0, st, a, r);
-        else hipLaunchKernelGGL((k_logprob_pd_reduced<P, BLK_SMALL, false, COMP>), dim3(grid), dim3(BLK_SMALL), 0, st, a, r);
+        with_flag(vec, [&](auto v) {
+            hipLaunchKernelGGL((k_logprob_pd_reduced<P, BLK_SMALL, v, COMP>), dim3(grid), dim3(BLK_SMALL), 0, st, a, r);
+        });
     } else {
         // the plain form is HBM-bound: 128-lane workgroups stream best; the compensated one is
         // VALU-bound (~11 flops per matrix entry): 256 lanes, like the other compute-bound kernels
         constexpr int BLK = COMP ? BLK_LARGE : BLK_STREAM;
         const unsigned grid = (unsigned)((W + BLK - 1) / BLK);
-        if (vec) hipLaunchKernelGGL((k_logprob_pd_reduced<P, BLK, true, COMP>), dim3(grid), dim3(BLK), 0, st, a, r);
-        else hipLaunchKernelGGL((k_logprob_pd_reduced<P, BLK, false, COMP>), dim3(grid), dim3(BLK), 0, st, a, r);
+        with_flag(vec, [&](auto v) { hipLaunchKernelGGL((k_logprob_pd_reduced<P, BLK, v, COMP>), dim3(grid), dim3(BLK), 0, st, a, r); });
     }
     HIP_TRY(hipGetLastError());
     return BISIP_OK;
@@ -93,10 +94,10 @@ template <int P>
 int launch_faithful(const bisip_ctx *c, const double *theta, int64_t W, double *out, hipStream_t st)
 {
     const LaunchArgs a = make_args(c, theta, out, W, c->d_cb_faithful);
-    const bool vec = ((uintptr_t)theta % 16) == 0;
     const unsigned grid = (unsigned)((W + BLK_SMALL - 1) / BLK_SMALL);
-    if (vec) hipLaunchKernelGGL((k_logprob_pd_faithful<P, BLK_SMALL, true>), dim3(grid), dim3(BLK_SMALL), 0, st, a, c->S);
-    else hipLaunchKernelGGL((k_logprob_pd_faithful<P, BLK_SMALL, false>), dim3(grid), dim3(BLK_SMALL), 0, st, a, c->S);
+    with_flag(aligned16(theta), [&](auto v) {
+        hipLaunchKernelGGL((k_logprob_pd_faithful<P, BLK_SMALL, v>), dim3(grid), dim3(BLK_SMALL), 0, st, a, c->S);
+    });
     HIP_TRY(hipGetLastError());
     return BISIP_OK;
 }
@@ -121,8 +122,7 @@ int launch_logprob_batch(const bisip_ctx *c, const double *theta, int64_t W, dou
     BatchArgs a = make_batch_args(c, theta, out, W);
     if (c->d_cb_lp) a.cb = c->d_cb_lp;
     const unsigned grid = (unsigned)((W + 63) / 64);
-    if (a.Wp % 64 == 0) hipLaunchKernelGGL((k_logprob_batch<M, true>), dim3(grid), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((k_logprob_batch<M, false>), dim3(grid), dim3(64), 0, st, a);
+    with_flag(a.Wp % 64 == 0, [&](auto whole) { hipLaunchKernelGGL((k_logprob_batch<M, whole>), dim3(grid), dim3(64), 0, st, a); });
     HIP_TRY(hipGetLastError());
     return BISIP_OK;
 }
@@ -133,54 +133,29 @@ int launch_reduced_batch(const bisip_ctx *c, const double *theta, int64_t W, dou
     const BatchArgs a = make_batch_args(c, theta, out, W);
     constexpr int BLK = COMP ? BLK_LARGE : BLK_STREAM;
     if (W >= SMALL_W && a.Wp % BLK == 0) {      // bulk evaluation: stream like the single-spectrum kernel
-        const unsigned sgrid = (unsigned)((W + BLK - 1) / BLK);
-        if (((uintptr_t)theta % 16) == 0) hipLaunchKernelGGL((k_logprob_batch_reduced_stream<P, BLK, true, COMP>), dim3(sgrid), dim3(BLK), 0, st, a);
-        else hipLaunchKernelGGL((k_logprob_batch_reduced_stream<P, BLK, false, COMP>), dim3(sgrid), dim3(BLK), 0, st, a);
-        HIP_TRY(hipGetLastError());
-        return BISIP_OK;
+        const unsigned grid = (unsigned)((W + BLK - 1) / BLK);
+        with_flag(aligned16(theta), [&](auto v) {
+            hipLaunchKernelGGL((k_logprob_batch_reduced_stream<P, BLK, v, COMP>), dim3(grid), dim3(BLK), 0, st, a);
+        });
+    } else {
+        const unsigned grid = (unsigned)((W + 63) / 64);
+        with_flag(a.Wp % 64 == 0, [&](auto whole) {
+            hipLaunchKernelGGL((k_logprob_batch_reduced<P, whole, COMP>), dim3(grid), dim3(64), 0, st, a);
+        });
     }
-    const unsigned grid = (unsigned)((W + 63) / 64);
-    if (a.Wp % 64 == 0) hipLaunchKernelGGL((k_logprob_batch_reduced<P, true, COMP>), dim3(grid), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((k_logprob_batch_reduced<P, false, COMP>), dim3(grid), dim3(64), 0, st, a);
     HIP_TRY(hipGetLastError());
     return BISIP_OK;
 }
 
 int dispatch_logprob_batch(const bisip_ctx *c, const double *theta, int64_t W, double *out, hipStream_t st)
 {
-    switch (c->model_id) {
-    case BISIP_MODEL_POLYDECOMP:
-        if (effective_variant(c) == BISIP_VARIANT_REDUCED) {
-            switch (c->P) {
-#define X(p) case p: return launch_reduced_batch<p, false>(c, theta, W, out, st);
-                X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10)
-#undef X
-            }
-        } else if (effective_variant(c) == BISIP_VARIANT_REDUCED_COMP) {
-            switch (c->P) {
-#define X(p) case p: return launch_reduced_batch<p, true>(c, theta, W, out, st);
-                X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10)
-#undef X
-            }
-        } else {
-            switch (c->P) {
-#define X(p) case p: return launch_logprob_batch<PDCollapsed<p>>(c, theta, W, out, st);
-                X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10)
-#undef X
-            }
-        }
-        break;
-    case BISIP_MODEL_COLECOLE:
-        switch (c->D) {
-#define X(d) case d: return launch_logprob_batch<ColeCole<d>>(c, theta, W, out, st);
-            X(1) X(2) X(3) X(4) X(5)
-#undef X
-        }
-        break;
-    case BISIP_MODEL_DIAS2000: return launch_logprob_batch<Dias>(c, theta, W, out, st);
-    case BISIP_MODEL_SHIN2015: return launch_logprob_batch<Shin>(c, theta, W, out, st);
+    const char *what = "batch log-probability";
+    if (c->model_id == BISIP_MODEL_POLYDECOMP) {
+        const int v = effective_variant(c);
+        if (v == BISIP_VARIANT_REDUCED) return with_pd_degree(c, what, [&](auto p) { return launch_reduced_batch<p, false>(c, theta, W, out, st); });
+        if (v == BISIP_VARIANT_REDUCED_COMP) return with_pd_degree(c, what, [&](auto p) { return launch_reduced_batch<p, true>(c, theta, W, out, st); });
     }
-    return fail(BISIP_EUNSUPPORTED, "no batch kernel for this model shape");
+    return with_model(c, what, [&](auto m) { return launch_logprob_batch<typename decltype(m)::type>(c, theta, W, out, st); });
 }
 
 }  // namespace
@@ -207,54 +182,21 @@ int dispatch_logprob(const bisip_ctx *c, const double *theta, int64_t W, double 
         if (W > 0xffffffffLL) return fail(BISIP_EINVAL, "W=%lld: a batch context takes fewer than 2^32 rows per call", (long long)W);
         return dispatch_logprob_batch(c, theta, W, out, st);
     }
-    switch (c->model_id) {
-    case BISIP_MODEL_POLYDECOMP: {
+    const char *what = "log-probability";
+    if (c->model_id == BISIP_MODEL_POLYDECOMP) {
         const int v = effective_variant(c);
-        if (v == BISIP_VARIANT_REDUCED) {
-            switch (c->P) {
-#define X(p) case p: return launch_reduced<p, false>(c, theta, W, out, st);
-                PD_CASES(X)
-#undef X
-            }
-        } else if (v == BISIP_VARIANT_REDUCED_COMP) {
-            switch (c->P) {
-#define X(p) case p: return launch_reduced<p, true>(c, theta, W, out, st);
-                PD_CASES(X)
-#undef X
-            }
-        } else if (v == BISIP_VARIANT_COLLAPSED) {
-            switch (c->P) {
-#define X(p) case p: return launch_collapsed<p>(c, theta, W, out, st);
-                PD_CASES(X)
-#undef X
-            }
-        } else if (v == BISIP_VARIANT_WAVE) {
-            switch (c->P) {
-#define X(p) case p: return launch_wave<p>(c, theta, W, out, st);
-                PD_CASES(X)
-#undef X
-            }
-        } else if (v == BISIP_VARIANT_FAITHFUL) {
+        if (v == BISIP_VARIANT_REDUCED) return with_pd_degree(c, what, [&](auto p) { return launch_reduced<p, false>(c, theta, W, out, st); });
+        if (v == BISIP_VARIANT_REDUCED_COMP) return with_pd_degree(c, what, [&](auto p) { return launch_reduced<p, true>(c, theta, W, out, st); });
+        if (v == BISIP_VARIANT_COLLAPSED) return with_pd_degree(c, what, [&](auto p) { return launch_collapsed<p>(c, theta, W, out, st); });
+        if (v == BISIP_VARIANT_WAVE) return with_pd_degree(c, what, [&](auto p) { return launch_wave<p>(c, theta, W, out, st); });
+        if (v == BISIP_VARIANT_FAITHFUL) {
             if (!c->d_cb_faithful) return fail(BISIP_EUNSUPPORTED, "the faithful formulation is not available for this context");
-            switch (c->P) {
-#define X(p) case p: return launch_faithful<p>(c, theta, W, out, st);
-                PD_CASES(X)
-#undef X
-            }
+            return with_pd_degree(c, what, [&](auto p) { return launch_faithful<p>(c, theta, W, out, st); });
         }
         return fail(BISIP_EUNSUPPORTED, "no kernel for poly_deg=%d variant=%d", c->P, v);
     }
-    case BISIP_MODEL_COLECOLE:
-        switch (c->D) {
-#define X(d) case d: return launch_logprob<ColeCole<d>>(c, theta, W, out, st);
-            CC_CASES(X)
-#undef X
-        }
-        return fail(BISIP_EUNSUPPORTED, "no kernel for n_modes=%d", c->D);
-    case BISIP_MODEL_DIAS2000: return launch_logprob<Dias>(c, theta, W, out, st);
-    case BISIP_MODEL_SHIN2015: return launch_logprob<Shin>(c, theta, W, out, st);
-    }
-    return fail(BISIP_EINVAL, "bad model_id %d", c->model_id);
+    // (PolynomialDecomposition has returned: its k_logprob<PDCollapsed<P>> are those of launch_collapsed)
+    return with_model(c, what, [&](auto m) { return launch_logprob<typename decltype(m)::type>(c, theta, W, out, st); });
 }
 
 }  // namespace host

@@ -194,25 +194,7 @@ int launch_response(const RmArgs &a, unsigned blocks, int kind, hipStream_t st)
 
 int dispatch_response(const bisip_ctx *c, const RmArgs &a, unsigned blocks, int kind, hipStream_t st)
 {
-    switch (c->model_id) {
-    case BISIP_MODEL_POLYDECOMP:
-        switch (c->P) {
-#define X(p) case p: return launch_response<PDCollapsed<p>>(a, blocks, kind, st);
-            PD_CASES(X)
-#undef X
-        }
-        break;
-    case BISIP_MODEL_COLECOLE:
-        switch (c->D) {
-#define X(d) case d: return launch_response<ColeCole<d>>(a, blocks, kind, st);
-            CC_CASES(X)
-#undef X
-        }
-        break;
-    case BISIP_MODEL_DIAS2000: return launch_response<Dias>(a, blocks, kind, st);
-    case BISIP_MODEL_SHIN2015: return launch_response<Shin>(a, blocks, kind, st);
-    }
-    return fail(BISIP_EUNSUPPORTED, "no response-moments kernel for this model shape");
+    return with_model(c, "response-moments", [&](auto m) { return launch_response<typename decltype(m)::type>(a, blocks, kind, st); });
 }
 
 // bytes of the segments' sums and the shifts; 0 with one segment, -1 when the grid does not exist

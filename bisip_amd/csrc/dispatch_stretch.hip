@@ -63,54 +63,28 @@ int dispatch_stretch(const bisip_ctx *c, const StretchWork &a, long long Wp, hip
         if (Wp < 2 || (Wp & 1)) return fail(BISIP_EINVAL, "batch context: walkers_per_spectrum must be even and >= 2, got %lld", Wp);
         return dispatch_stretch_batch(c, a, Wp, st);
     }
-    switch (c->model_id) {
-    case BISIP_MODEL_POLYDECOMP:
+    if (c->model_id == BISIP_MODEL_POLYDECOMP) {
+        const int v = effective_variant(c);
         // the sampler kernels exist for the reduced and the collapsed formulation only; running
         // another one here would store log-probabilities that bisip_logprob does not reproduce
         // bit for bit, so say so and let the caller drive the move from the host
-        if (effective_variant(c) == BISIP_VARIANT_FAITHFUL || effective_variant(c) == BISIP_VARIANT_WAVE)
+        if (v == BISIP_VARIANT_FAITHFUL || v == BISIP_VARIANT_WAVE)
             return fail(BISIP_EUNSUPPORTED, "the device stretch move has no kernel for the faithful / wave "
                         "formulation: use variant auto, reduced or collapsed, or the host-loop sampler");
-        if (effective_variant(c) == BISIP_VARIANT_REDUCED) {
-            switch (c->P) {
-#define X(p) case p: return stretch_reduced<p, false>(c, a, st);
-                PD_CASES(X)
-#undef X
-            }
-        } else if (effective_variant(c) == BISIP_VARIANT_REDUCED_COMP) {
-            switch (c->P) {
-#define X(p) case p: return stretch_reduced<p, true>(c, a, st);
-                PD_CASES(X)
-#undef X
-            }
-        } else {
-            switch (c->P) {
-#define X(p) case p: return stretch_generic<PDCollapsed<p>>(c, a, st);
-                PD_CASES(X)
-#undef X
-            }
-        }
-        break;
-    case BISIP_MODEL_COLECOLE:
-        switch (c->D) {
-#define X(d) case d: return stretch_generic<ColeCole<d>>(c, a, st);
-            CC_CASES(X)
-#undef X
-        }
-        break;
-    case BISIP_MODEL_DIAS2000: return stretch_generic<Dias>(c, a, st);
-    case BISIP_MODEL_SHIN2015: return stretch_generic<Shin>(c, a, st);
+        if (v == BISIP_VARIANT_REDUCED) return with_pd_degree(c, "stretch", [&](auto p) { return stretch_reduced<p, false>(c, a, st); });
+        if (v == BISIP_VARIANT_REDUCED_COMP) return with_pd_degree(c, "stretch", [&](auto p) { return stretch_reduced<p, true>(c, a, st); });
     }
-    return fail(BISIP_EUNSUPPORTED, "no stretch kernel for this model shape");
+    return with_model(c, "stretch", [&](auto m) { return stretch_generic<typename decltype(m)::type>(c, a, st); });
 }
 
 int dispatch_apply(const bisip_ctx *c, const StretchArgs &a, hipStream_t st)
 {
     const unsigned grid = (unsigned)((a.n_slots + 63) / 64);
     switch (c->ndim) {
-#define X(n) case n: hipLaunchKernelGGL((k_stretch_apply<n>), dim3(grid), dim3(64), 0, st, a); break;
-        X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
-#undef X
+#define NDIM_CASE(n) case n: hipLaunchKernelGGL((k_stretch_apply<n>), dim3(grid), dim3(64), 0, st, a); break;
+        NDIM_CASE(1) NDIM_CASE(2) NDIM_CASE(3) NDIM_CASE(4) NDIM_CASE(5) NDIM_CASE(6) NDIM_CASE(7) NDIM_CASE(8)
+        NDIM_CASE(9) NDIM_CASE(10) NDIM_CASE(11) NDIM_CASE(12) NDIM_CASE(13) NDIM_CASE(14) NDIM_CASE(15) NDIM_CASE(16)
+#undef NDIM_CASE
     default: return fail(BISIP_EUNSUPPORTED, "ndim=%d", c->ndim);
     }
     HIP_TRY(hipGetLastError());

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/bisip_hip.h"
@@ -34,8 +35,13 @@ constexpr long long SMALL_W = 256LL * 256 * 2;  // below this, 64-lane workgroup
 constexpr int REDUCED_COMP_MEMORY_OPERANDS_FROM = 6;
 constexpr double BISIP_REDUCED_ERR_MAX = 1e-12;  // AUTO keeps the QR-reduced form below this estimate
 
+// The model shapes that have kernels: the only lists of them (with_model and with_pd_degree below expand them)
 #define PD_CASES(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10)
 #define CC_CASES(X) X(1) X(2) X(3) X(4) X(5)
+#define X(n) +1
+static_assert(0 PD_CASES(X) == BISIP_MAX_POLY_DEG + 1, "PD_CASES lists the degrees 0 ... BISIP_MAX_POLY_DEG");
+static_assert(0 CC_CASES(X) == BISIP_MAX_MODES, "CC_CASES lists the mode counts 1 ... BISIP_MAX_MODES");
+#undef X
 
 }  // namespace host
 }  // namespace bisip
@@ -131,6 +137,59 @@ inline void fill_reduced(const bisip_ctx *c, ReducedArgs<P, COMP> &r)
     std::memcpy(r.elo, t.elo.data(), sizeof(r.elo));
     r.rest = t.rest;
 }
+
+// A context's model shape as a template argument, for every host entry point that launches a model-templated kernel.
+// with_model(c, what, f) returns f(ModelTag<M>{}), M = PDCollapsed<P>, ColeCole<D>, Dias or Shin;
+// with_pd_degree(c, what, f) returns f(std::integral_constant<int, P>{}), for the PolynomialDecomposition formulations
+// whose kernels are templated on the degree itself.  They know shapes, not policy: which formulation runs is the
+// caller's business (effective_variant).  `what` names the kernel family in the error text.  build_context refuses
+// every shape outside the lists, so the fall-throughs cannot be reached through the ABI: one code and one wording
+// for all of them is no change of behaviour.
+template <class M> struct ModelTag { using type = M; };
+
+template <class F>
+inline int with_pd_degree(const bisip_ctx *c, const char *what, F &&f)
+{
+    switch (c->P) {
+#define X(p) case p: return f(std::integral_constant<int, p>{});
+        PD_CASES(X)
+#undef X
+    }
+    return fail(BISIP_EUNSUPPORTED, "no %s kernel for poly_deg=%d", what, c->P);
+}
+
+template <class F>
+inline int with_model(const bisip_ctx *c, const char *what, F &&f)
+{
+    switch (c->model_id) {
+    case BISIP_MODEL_POLYDECOMP:
+        switch (c->P) {
+#define X(p) case p: return f(ModelTag<PDCollapsed<p>>{});
+            PD_CASES(X)
+#undef X
+        }
+        return fail(BISIP_EUNSUPPORTED, "no %s kernel for poly_deg=%d", what, c->P);
+    case BISIP_MODEL_COLECOLE:
+        switch (c->D) {
+#define X(d) case d: return f(ModelTag<ColeCole<d>>{});
+            CC_CASES(X)
+#undef X
+        }
+        return fail(BISIP_EUNSUPPORTED, "no %s kernel for n_modes=%d", what, c->D);
+    case BISIP_MODEL_DIAS2000: return f(ModelTag<Dias>{});
+    case BISIP_MODEL_SHIN2015: return f(ModelTag<Shin>{});
+    }
+    return fail(BISIP_EUNSUPPORTED, "no %s kernel for model_id=%d", what, c->model_id);
+}
+
+// a runtime flag as a template argument: f(std::bool_constant<b>{})
+template <class F>
+inline auto with_flag(bool b, F &&f)
+{
+    if (b) return f(std::bool_constant<true>{});
+    return f(std::bool_constant<false>{});
+}
+
 LaunchArgs make_args(const bisip_ctx *c, const double *theta, double *out, int64_t W, const double *cb);
 BatchArgs make_batch_args(const bisip_ctx *c, const double *theta, double *out, int64_t W);
 

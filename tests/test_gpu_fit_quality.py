@@ -140,6 +140,9 @@ CASES = [('PolynomialDecomposition', dict(poly_deg=0), 3, 1, 1, 1),
          ('PeltonColeCole', dict(n_modes=2), 32, 1, 5, 500),
          ('PolynomialDecomposition', dict(poly_deg=5), 20, 3, 5, 500),
          ('PeltonColeCole', dict(n_modes=2), 20, 256, 3, 9)]
+# the other shapes a context can have, at the smallest sizes above: each of the 18 takes a kernel of its own
+CASES += [('PolynomialDecomposition', dict(poly_deg=p), 3 if p <= 2 else 20, 1, 1 + p % 3, 64 - 3 * p) for p in (1, 2, 3, 4, 6, 7, 8, 9, 10)]
+CASES += [('PeltonColeCole', dict(n_modes=d), 20, 1, d - 2, 9 * d) for d in (3, 4, 5)]
 
 
 @pytest.mark.parametrize('model,kw,n_freq,E,Wp,n', CASES, ids=lambda v: v if isinstance(v, str) else None)

@@ -149,6 +149,9 @@ CASES = [('PolynomialDecomposition', dict(poly_deg=0), 20, 8, 40),
          ('Dias2000', {}, 32, 64, 47),
          ('Shin2015', {}, 20, 8, 55),
          ('PeltonColeCole', dict(n_modes=2), 32, 8, 43)]
+# the other shapes a context can have, at the smallest sizes above: each of the 18 takes a kernel of its own
+CASES += [('PolynomialDecomposition', dict(poly_deg=p), 20, 8, 36 + p) for p in (1, 2, 3, 4, 6, 7, 8, 9)]
+CASES += [('PeltonColeCole', dict(n_modes=d), 20, 8, 38 + d) for d in (4, 5)]
 
 
 @pytest.mark.parametrize('model,kw,n_freq,Wp,stored', CASES, ids=lambda v: v if isinstance(v, str) else None)
