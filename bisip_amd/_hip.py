@@ -190,6 +190,10 @@ SYMBOLS = {
     'bisip_fit_quality_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                              ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    'bisip_predictive_check_workspace': (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    'bisip_predictive_check_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                                  ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     'bisip_columns_percentiles_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int,
                                                      ctypes.c_void_p, ctypes.c_void_p]),
     'bisip_q_columns_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
@@ -777,6 +781,23 @@ class HipContext:
                                                int(n_samples), int(sample_stride), int(walkers_per_ensemble),
                                                d_mean_q_ptr or None, d_var_q_ptr or None, d_lmeh_ptr or None,
                                                d_work_ptr or None, int(work_bytes), ctypes.c_void_p(stream)))
+
+    def predictive_check_workspace(self, n_samples, n_spectra, walkers_per_ensemble):
+        """Bytes of device scratch predictive_check_dev needs (always positive; negative: shape not supported)."""
+        return int(self._lib.bisip_predictive_check_workspace(self._h, int(n_samples), int(n_spectra), int(walkers_per_ensemble)))
+
+    def predictive_check_dev(self, first_spectrum, n_spectra, d_chain_ptr, n_samples, sample_stride, walkers_per_ensemble,
+                             d_pit_ptr, d_row_ptr, d_sign_changes_ptr, d_work_ptr=0, work_bytes=0, stream=0):
+        """Posterior predictive checks over the used samples of ``n_spectra`` spectra (bisip_amd.predictive): d_pit
+        (n_spectra, 2, N), the mean of ``Phi((y - forward) / sigma)``; d_row (n_spectra, 3), the means of the chi-square
+        ``T``, of ``P(chi2_2N >= T)`` and of ``P(max of 2N |eps| >= the largest standardised residual)``; d_sign_changes
+        (n_spectra, 2N - 1) int64, the histogram of the residual's sign changes along the frequency axis; any 0 / None but
+        not all.  ``d_chain_ptr``: walker 0 of ``first_spectrum`` in the first used sample.  Device pointers (ints),
+        asynchronous on ``stream``."""
+        _check(self._lib.bisip_predictive_check_dev(self._h, int(first_spectrum), int(n_spectra), d_chain_ptr or None,
+                                                    int(n_samples), int(sample_stride), int(walkers_per_ensemble),
+                                                    d_pit_ptr or None, d_row_ptr or None, d_sign_changes_ptr or None,
+                                                    d_work_ptr or None, int(work_bytes), ctypes.c_void_p(stream)))
 
     def q_columns_dev(self, first_spectrum, n_spectra, d_cols_ptr, rows_per_spectrum, stream=0):
         """The Re / Im columns ``(n_spectra, 2N, rows_per_spectrum)`` that forward_columns_dev wrote become, in place, the

@@ -18,6 +18,7 @@ from .fitquality import BatchFitQuality
 from .interval import BatchIntervals
 from .dist import shard_range
 from .loo import BatchLoo
+from .predictive import BatchPredictive
 from .evidence import BatchEvidence
 from .response import BatchResponse
 from .sampler import DeviceEnsembleSampler
@@ -55,7 +56,7 @@ def default_params(model, n_modes=1, poly_deg=5):
 
 
 class SpectraBatch(BatchCovariance, BatchIntervals, BatchEss, BatchDiagnostics, BatchResponse, BatchFitQuality, BatchLoo,
-                   BatchEvidence, decomposition.BatchRelaxation):
+                   BatchEvidence, BatchPredictive, decomposition.BatchRelaxation):
     """E spectra inverted together with the same model class.
 
     Args:

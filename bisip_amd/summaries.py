@@ -19,6 +19,7 @@ from .diagnostics import device_ess_sd, device_mcse_sd, device_rank_rhat, device
 from .ess import device_ess, device_mcse_mean
 from .fitquality import device_fit_quality
 from .interval import device_hdi
+from .predictive import device_predictive_check
 from .response import device_model_moments
 from .trace import device_trace
 
@@ -337,3 +338,13 @@ class DeviceChainSummaries:
         one pass over the chain where it lies (bisip_fit_quality_dev; ``chain_on_device``), else over an upload of the
         used samples only.  No response is stored."""
         return device_fit_quality(self.used_samples_dev(discard, thin), self.backend.ctx)
+
+    def predictive_check(self, discard=0, thin=1):
+        """``(pit, row, sign_changes)`` of every ensemble's spectrum over the used samples: ``pit (n_ensembles, 2, N)`` the
+        posterior predictive probability ``P(y_rep <= y | y)`` of every data point, ``row (n_ensembles, 3)`` the means of
+        the chi-square ``T``, of ``P(chi2_2N >= T)`` and of the probability of the largest standardised residual, and
+        ``sign_changes (n_ensembles, 2N - 1)`` the histogram of the residual's sign changes along the frequency axis
+        (bisip_amd.predictive.predictive_sums), evaluated and summed over the chain where it lies
+        (bisip_predictive_check_dev; ``chain_on_device``), else over an upload of the used samples only.  No response is
+        stored."""
+        return device_predictive_check(self.used_samples_dev(discard, thin), self.backend.ctx)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Which model does the spectrum support: Pelton Cole-Cole with one mode and with two, fitted to the same spectrum and
-ranked by WAIC, by PSIS-LOO and by their marginal likelihood (bridge sampling), and where the better one still misses the
-data.  The chains stay on the GPU; the sums over them (bisip_fit_quality_dev), the Pareto-smoothed tails of every data point
+ranked by WAIC, by PSIS-LOO and by their marginal likelihood (bridge sampling), whether each fits the spectrum within its
+errors at all (posterior predictive checks), and where the better one still misses the data.  The chains stay on the GPU;
+the sums over them (bisip_fit_quality_dev, bisip_predictive_check_dev), the Pareto-smoothed tails of every data point
 (bisip_loo_columns_dev) and the bridge-sampling iteration (bisip_bridge_*_dev) are taken there."""
 import os
 import sys
@@ -16,7 +17,7 @@ from bisip_amd.fitquality import compare_waic
 from bisip_amd.loo import compare_loo
 
 filepath = DataFiles()['SIP-K389174']                         # two bumps in its imaginary part (docs/tutorials/pelton.ipynb)
-results, loos, evidences, models = {}, {}, {}, {}
+results, loos, evidences, checks, models = {}, {}, {}, {}, {}
 for n_modes in (1, 2):
     np.random.seed(42)
     model = PeltonColeCole(filepath, nwalkers=64, nsteps=2000, n_modes=n_modes)
@@ -26,6 +27,7 @@ for n_modes in (1, 2):
     name = f'{n_modes} mode' + 's' * (n_modes > 1)
     results[name], loos[name], models[name] = model.get_waic(discard=1000), model.get_loo(discard=1000), model
     evidences[name] = model.get_evidence(discard=1000)          # the log marginal likelihood by bridge sampling
+    checks[name] = model.get_predictive_check(discard=1000)     # does the model reproduce the data within their errors
     dic = model.get_dic(discard=1000)
     print(f'{name}: DIC {dic["dic"]:.1f}, p_D {dic["p_d"]:.1f}; {results[name]["n_high"]} points with p_waic > 0.4')
 
@@ -42,6 +44,12 @@ for row in compare_loo(loos):
 print('model      log_evidence   log_bf    prob      se')
 for row in compare_evidence(evidences):
     print(f'{row["name"]:<10} {row["log_evidence"]:12.2f} {row["log_bf"]:8.2f} {row["prob"]:7.3f} {row["se"]:7.2f}')
+
+# the criteria above are relative; the predictive checks are not: chi2_reduced near 1 and no probability near 0 is a fit.  A
+# small p_runs: the residuals run in bands along the frequency axis, the model misses the spectrum's shape
+print('model      chi2_reduced   p_chi2   p_runs    p_max  n_extreme')
+for name, c in checks.items():
+    print(f'{name:<10} {c["chi2_reduced"]:12.2f} {c["p_chi2"]:8.3g} {c["p_runs"]:8.3g} {c["p_max"]:8.3g} {c["n_extreme"]:10d}')
 
 best = compare_waic(results)[0]['name']
 misfit = models[best].get_pointwise_misfit(discard=1000)      # (2, N): near 1, the point is fitted to its error bar

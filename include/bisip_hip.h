@@ -48,8 +48,8 @@ extern "C" {
  *    then chain_cov_dev and chain_best_sample_dev (+ _workspace), then forward_columns_kind_dev,
  *    forward_percentiles_kind and response_moments_dev (+ _workspace) with BISIP_RESPONSE_RI / _PA, then
  *    fit_quality_dev (+ _workspace), then reduced_emulate and ctx_reduced_operands, then q_columns_dev and
- *    loo_columns_dev (+ _workspace), then rtd_descriptors_dev and rtd_descriptors_host
- *    came later under the same number (additions only: a caller that needs them looks the symbols up). */
+ *    loo_columns_dev (+ _workspace), then rtd_descriptors_dev and rtd_descriptors_host, then predictive_check_dev
+ *    (+ _workspace) came later under the same number (additions only: a caller that needs them looks the symbols up). */
 #define BISIP_ABI_VERSION 6
 
 /* model_id -- the four reference model classes (src/bisip/models.py:182,232,274,308) */
@@ -757,6 +757,42 @@ int64_t bisip_fit_quality_workspace(bisip_ctx *ctx, int64_t n_samples, int64_t n
 int bisip_fit_quality_dev(bisip_ctx *ctx, int64_t first_spectrum, int64_t n_spectra, const double *d_chain,
                           int64_t n_samples, int64_t sample_stride, int64_t walkers_per_ensemble, double *d_mean_q,
                           double *d_var_q, double *d_lmeh, void *d_work, int64_t work_bytes, void *stream);
+
+/* POSTERIOR PREDICTIVE CHECKS of every spectrum over the used samples of a chain resident in device memory
+ * (bisip_amd/predictive.py holds the definitions: predictive_sums, predictive_check).  The noise is Gaussian with known
+ * sigma, so every check is the mean over the R rows of a closed-form function of the row's residuals; no random numbers.
+ * Per row and point, d = y - Z, t = d * d, q = t * iv as for bisip_fit_quality_dev; per row, T = sum of q (frequencies
+ * ascending, Re before Im of each, from 0.0), qmax = max q and C = the adjacent frequency pairs, within Re and within Im,
+ * whose d < 0 differs (0 ... 2N - 2).
+ *   d_pit (n_spectra, 2, N)          = mean of Phi(d sqrt(iv)) = P(y_rep <= y | y) of the point, evaluated as erfc(-a) / 2
+ *                                      with h = sqrt(iv / 2) correctly rounded (the halving is exact) and a = d * h,
+ *   d_row (n_spectra, 3)             = chi2_mean = mean of T;  p_chi2 = mean of Q(N, T / 2), Q the regularised upper
+ *                                      incomplete gamma function = P(chi2_2N >= T);  p_max = mean of
+ *                                      -expm1(2N * log1p(-erfc(sqrt(qmax / 2)))) = P(max of 2N |eps| >= sqrt(qmax)),
+ *   d_sign_changes (n_spectra, 2N-1) = the histogram of C (int64),
+ * any may be NULL, not all three; an output not asked for stays untouched.  Q(N, x) = exp(-x) sum_{k < N} x^k / k! with
+ * every term positive: x < N ascending from exp(-x), term = (term * x) / k; x >= N descending from
+ * exp(((N - 1) log x - x) - log((N - 1)!)), term = (term * k) / x; a sum that rounds above 1 is 1; the host passes
+ * log((N - 1)!), summed in long double.
+ * Chain layout, d_chain, first_spectrum, argument checks, error codes and the alignment rule: those of
+ * bisip_fit_quality_dev; fused in the same way, the model evaluated in registers, no response and no residual written.  A
+ * row with a parameter that is not finite, or whose T is not finite, counts in no bin and makes d_pit and d_row of ITS
+ * spectrum NaN and no other spectrum's: the bins of a spectrum add up to its good rows.
+ * Order.  Segments and row slots are those of bisip_fit_quality_dev (the same plan; a slot takes its rows in ascending
+ * order; slots pairwise within each run of 64, 32, 16, ..., 1 apart, the four runs then in ascending order; segments in
+ * ascending order), plain sums from 0.0 (every term is in [0, 1] or >= 0: no shift), divided by R at the end; nothing is
+ * fused.  The histogram: 32-bit integer atomics in LDS per workgroup, 64-bit integer atomics into the output, which the
+ * entry point zeroes on the stream: any order gives the same counts.  No floating-point atomics: the same bits on every
+ * call (predictive.ordered_predictive_sums gives those of chi2_mean and the counts in NumPy from the same responses, and
+ * the others in the same order with glibc's functions).  exp, log, log1p, expm1, erfc are the device library's.  (The row
+ * sums take one pass over the chain, pit a second in tiles of 8 frequencies; the tiling changes no output.)
+ * d_work: bisip_predictive_check_workspace() BYTES (always > 0; < 0: shape not supported), the segments' sums, 8-byte
+ * aligned.  BISIP_EUNSUPPORTED for d_row or d_sign_changes above N = 700, where exp(-x) underflows with x < N (d_pit alone
+ * is served).  64-bit offsets.  Asynchronous on stream, no host synchronisation. */
+int64_t bisip_predictive_check_workspace(bisip_ctx *ctx, int64_t n_samples, int64_t n_spectra, int64_t walkers_per_ensemble);
+int bisip_predictive_check_dev(bisip_ctx *ctx, int64_t first_spectrum, int64_t n_spectra, const double *d_chain,
+                               int64_t n_samples, int64_t sample_stride, int64_t walkers_per_ensemble, double *d_pit,
+                               double *d_row, long long *d_sign_changes, void *d_work, int64_t work_bytes, void *stream);
 
 /* PSIS-LOO, step 1: the Re / Im columns that bisip_forward_columns_dev wrote for n_spectra consecutive spectra starting
  * with first_spectrum -- d_cols (n_spectra, 2N, rows_per_spectrum) -- become, where they lie, the squared standardised
