@@ -15,6 +15,7 @@ from .autocorr import AutocorrError
 from .batch import SpectraBatch
 from .decomposition import DESCRIPTOR_NAMES, INTEGRATING_NAMES, integrating_params, rtd, rtd_descriptors
 from .data import DataFiles
+from .modes import MODE_NAMES, mode_descriptors, order_modes
 from .models import (ColeCole, Dias2000, Inversion, PeltonColeCole, PolynomialDecomposition,
                      Shin2015)
 from .sampler import DeviceEnsembleSampler, EnsembleSampler
@@ -23,4 +24,4 @@ from .utils import load_data, load_data_batch
 __all__ = ('Inversion', 'PolynomialDecomposition', 'PeltonColeCole', 'ColeCole', 'Dias2000',
            'Shin2015', 'DataFiles', 'SpectraBatch', 'EnsembleSampler', 'DeviceEnsembleSampler',
            'load_data', 'load_data_batch', 'AutocorrError', 'INTEGRATING_NAMES', 'rtd', 'integrating_params',
-           'rtd_descriptors', 'DESCRIPTOR_NAMES')
+           'rtd_descriptors', 'DESCRIPTOR_NAMES', 'MODE_NAMES', 'order_modes', 'mode_descriptors')

@@ -115,6 +115,10 @@ SYMBOLS = {
                                                  ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     'bisip_rtd_descriptors_host': (ctypes.c_int, [_dp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                   ctypes.c_int, _dp, ctypes.c_int, _dp, ctypes.c_int, _dp]),
+    'bisip_mode_order_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4),
+    'bisip_mode_order_host': (ctypes.c_int, [_dp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                             ctypes.c_int, _dp, _dp, ctypes.POINTER(ctypes.c_ubyte)]),
     'bisip_chain_range_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 3),
     'bisip_chain_histograms_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
@@ -980,6 +984,37 @@ def rtd_descriptors_host(chain, n_samples, sample_stride, n_ensembles, walkers_p
                                                      int(walkers_per_ensemble), ndim, _p(log_tau), log_tau.size,
                                                      _p(q), q.size, _p(out)))
     return out
+
+
+def mode_order_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, n_modes, key_group,
+                   d_ordered_ptr, d_desc_ptr, d_moved_ptr, stream=0):
+    """The modes of every used sample of a PeltonColeCole chain in the order of ``key_group`` (0: m, 1: log_tau, 2: c) into
+    d_ordered (n_samples, n_ensembles * walkers_per_ensemble, 1 + 3 n_modes), their descriptors (m_total, log_tau_cc...,
+    log_tau_peak...) into d_desc (..., 1 + 2 n_modes) and whether the order differs from the stored one into d_moved (...)
+    uint8; each 0 / None when not asked for, one at least; device pointers (ints), asynchronous on ``stream``."""
+    _check(load_library().bisip_mode_order_dev(d_chain_ptr, int(n_samples), int(sample_stride), int(n_ensembles),
+                                               int(walkers_per_ensemble), int(n_modes), int(key_group), d_ordered_ptr or None,
+                                               d_desc_ptr or None, d_moved_ptr or None, stream))
+
+
+def mode_order_host(chain, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, n_modes, key_group, ordered=True,
+                    desc=True, moved=True, offset=0):
+    """Host-only, no GPU: the rows of bisip_mode_order_dev by the same row function on the CPU (bisip_mode_order_host).
+    ``chain``: a float64 array whose samples start ``offset`` doubles in and lie ``sample_stride`` doubles apart; returns
+    ``(ordered (n_samples, rows, 1 + 3 n_modes), desc (n_samples, rows, 1 + 2 n_modes), moved (n_samples, rows) bool)``,
+    None for an output that is not asked for."""
+    chain = _c(chain).ravel()
+    n, stride, rows, K, offset = int(n_samples), int(sample_stride), int(n_ensembles) * int(walkers_per_ensemble), int(n_modes), int(offset)
+    ndim = 1 + 3 * K
+    if n < 1 or rows < 1 or K < 1 or offset < 0 or stride < rows * ndim or offset + (n - 1) * stride + rows * ndim > chain.size:
+        raise ValueError('the samples asked for lie outside the chain array')
+    o = np.empty((n, rows, ndim)) if ordered else None
+    d = np.empty((n, rows, 1 + 2 * K)) if desc else None
+    mv = np.empty((n, rows), dtype=np.uint8) if moved else None
+    _check(load_library().bisip_mode_order_host(_p(chain[offset:]), n, stride, int(n_ensembles), int(walkers_per_ensemble), K,
+                                                int(key_group), None if o is None else _p(o), None if d is None else _p(d),
+                                                None if mv is None else mv.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte))))
+    return o, d, None if mv is None else mv.astype(bool)
 
 
 def chain_range_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, d_out_ptr,

@@ -18,6 +18,7 @@ from .fitquality import BatchFitQuality
 from .interval import BatchIntervals
 from .dist import shard_range
 from .loo import BatchLoo
+from .modes import BatchModes
 from .predictive import BatchPredictive
 from .evidence import BatchEvidence
 from .response import BatchResponse
@@ -56,7 +57,7 @@ def default_params(model, n_modes=1, poly_deg=5):
 
 
 class SpectraBatch(BatchCovariance, BatchIntervals, BatchEss, BatchDiagnostics, BatchResponse, BatchFitQuality, BatchLoo,
-                   BatchEvidence, BatchPredictive, decomposition.BatchRelaxation):
+                   BatchEvidence, BatchPredictive, decomposition.BatchRelaxation, BatchModes):
     """E spectra inverted together with the same model class.
 
     Args:

@@ -158,6 +158,18 @@ inline int with_pd_degree(const bisip_ctx *c, const char *what, F &&f)
     return fail(BISIP_EUNSUPPORTED, "no %s kernel for poly_deg=%d", what, c->P);
 }
 
+// a Cole-Cole mode count that comes without a context (a chain's, bisip_mode_order_dev): f(std::integral_constant<int, D>{})
+template <class F>
+inline int with_mode_count(int n_modes, const char *what, F &&f)
+{
+    switch (n_modes) {
+#define X(d) case d: return f(std::integral_constant<int, d>{});
+        CC_CASES(X)
+#undef X
+    }
+    return fail(BISIP_EUNSUPPORTED, "no %s kernel for n_modes=%d", what, n_modes);
+}
+
 template <class F>
 inline int with_model(const bisip_ctx *c, const char *what, F &&f)
 {

@@ -240,14 +240,21 @@ def _chain_arrays(chain, logp):
 
 
 def bridge_evidence(chain, logp, log_prob_fn, bounds=None, n_draws=None, seed=0, neff='ess', proposal=None, use_all=None,
-                    draws=None, tau=None, tol=TOL, maxiter=MAXITER, offset=np.nan, ensemble=0):
+                    draws=None, tau=None, tol=TOL, maxiter=MAXITER, offset=np.nan, ensemble=0, order=None):
     """The evidence of ONE ensemble in NumPy: ``chain (n, Wp, ndim)`` (or flat ``(N, ndim)``: one walker) with its stored
     log-probability ``logp`` and ``log_prob_fn(theta (m, ndim)) -> (m,)``.  ``bounds (2, ndim)``: the prior box (None: ``log_evidence
     = log_ml``).  ``neff``: ``'ess'`` (the median over the parameters of ``ess.ess(second half, 'mean')``, at most ``N1``), None
     (``N1``) or a number.  ``proposal=(mean, cov)`` replaces the fit; all used samples then enter the estimator unless
     ``use_all=False``.  ``draws=(theta, log_g)``: the proposal's draws, instead of ``host_draws(seed)``.  ``tau``: a number
-    replaces the estimate of ``series_tau``.  Returns the dict of ``get_evidence``."""
+    replaces the estimate of ``series_tau``.  ``order=(n_modes, by)``: a Cole-Cole chain whose modes share one box
+    (bisip_amd.modes): the samples are taken with their modes in order (their stored log-probability unchanged), a draw whose
+    modes are not in order gets ``logp = -inf`` (and counts in ``frac_outside``), ``log_symmetry = log(n_modes!)`` is added to
+    ``log_ml`` and ``log_evidence`` and returned beside them -- the estimate over one labelling, where a normal proposal fits.
+    Returns the dict of ``get_evidence``."""
     x, lp = _chain_arrays(chain, logp)
+    if order is not None:
+        from .modes import log_symmetry, modes_moved, order_modes
+        x = order_modes(x, *order)
     n, Wp, ndim = x.shape
     if proposal is None:
         n0, n1 = halves(n, Wp, ndim)
@@ -273,6 +280,8 @@ def bridge_evidence(chain, logp, log_prob_fn, bounds=None, n_draws=None, seed=0,
         theta2, lg2 = (np.asarray(a, dtype=np.float64) for a in draws)
         N2 = theta2.shape[0]
     lp2 = np.asarray(log_prob_fn(theta2), dtype=np.float64).reshape(N2)
+    if order is not None:
+        lp2 = np.where(modes_moved(theta2, *order), -np.inf, lp2)
     with np.errstate(all='ignore'):
         l2 = lp2 - lg2
     if neff is None:
@@ -294,9 +303,13 @@ def bridge_evidence(chain, logp, log_prob_fn, bounds=None, n_draws=None, seed=0,
     with np.errstate(all='ignore'):
         log_ml = it['log_r'] + float(lstar)
         se = float(np.sqrt(relative_error2(it['moments'], N1, N2, t)))
+    sym = {}
+    if order is not None:
+        sym = dict(log_symmetry=log_symmetry(order[0]))
+        log_ml = log_ml + sym['log_symmetry']
     return dict(log_evidence=log_ml - _log_volume(bounds, ndim), log_ml=log_ml, se=se, iterations=it['iterations'], n1=N1,
                 n2=N2, neff=ne, tau_f2=t, frac_outside=float(np.mean(np.isneginf(lp2))), gaussian_offset=float(offset),
-                proposal_mean=mu, proposal_cov=np.asarray(cov, dtype=np.float64).reshape(ndim, ndim))
+                proposal_mean=mu, proposal_cov=np.asarray(cov, dtype=np.float64).reshape(ndim, ndim), **sym)
 
 
 def compare_evidence(results):
@@ -402,7 +415,7 @@ def _tail_view(view, first, n):
 
 
 def device_evidence(view, logp_view, ctx, n_draws=None, seed=0, neff='ess', proposal=None, use_all=None, first_ensemble=0,
-                    tol=TOL, maxiter=MAXITER, keep_draws=False):
+                    tol=TOL, maxiter=MAXITER, keep_draws=False, order=None):
     """The bridge-sampling estimate of every ensemble of a ChainView with the stored log-probability of ``logp_view`` (a
     ChainView of ``ndim = 1`` over the same samples) and the model of ``ctx`` (a HipContext of ``view.n_ensembles`` spectra), where
     the chain lies: bisip_chain_cov_dev of the first half, the Cholesky factor on the host, bisip_bridge_logg_dev (``l1``),
@@ -412,7 +425,10 @@ def device_evidence(view, logp_view, ctx, n_draws=None, seed=0, neff='ess', prop
     the device.  Ensemble ``e`` draws from the Philox stream of ``first_ensemble + e``.  ``bisip_logprob_dev`` runs the formulation
     the context holds after the sampler's guard.  Returns a dict of ``(E,)`` arrays ``log_ml``, ``se``, ``iterations``, ``neff``,
     ``tau_f2``, ``frac_outside``, the ints ``n1`` and ``n2`` and ``proposal_mean (E, ndim)``, ``proposal_cov (E, ndim, ndim)``; with
-    ``keep_draws`` also ``theta2 (E, N2, ndim)``, ``logg2`` and ``logp2 (E, N2)`` (NumPy)."""
+    ``keep_draws`` also ``theta2 (E, N2, ndim)``, ``logg2`` and ``logp2 (E, N2)`` (NumPy).  ``order=(n_modes, by)`` as
+    ``bridge_evidence``: the samples are the ordered derived view (one bisip_mode_order_dev), every pass of draws takes one
+    more bisip_mode_order_dev that asks for ``moved`` alone and a ``masked_fill_`` of ``logp2`` (kept as filled); the dict gains
+    ``log_symmetry``."""
     import torch
     from . import _hip
     from .autocorr import device_integrated_time
@@ -420,6 +436,9 @@ def device_evidence(view, logp_view, ctx, n_draws=None, seed=0, neff='ess', prop
     n, E, Wp, ndim = view.n, view.n_ensembles, view.walkers_per_ensemble, view.ndim
     if ndim != ctx.ndim or E != ctx.n_spectra:
         raise ValueError(f'a chain of {E} ensembles of {ndim} parameters for a context of {ctx.n_spectra} spectra of {ctx.ndim}')
+    if order is not None:
+        from .modes import device_mode_order, key_group, log_symmetry
+        view = view.derived(device_mode_order(view, order[0], order[1], ordered=True, desc=False)[0])
     if (logp_view.n, logp_view.n_ensembles, logp_view.walkers_per_ensemble, logp_view.ndim) != (n, E, Wp, 1):
         raise ValueError('the log-probability does not belong to the samples of the chain')
     if proposal is None:
@@ -465,7 +484,11 @@ def device_evidence(view, logp_view, ctx, n_draws=None, seed=0, neff='ess', prop
         _hip.bridge_draw_dev(d_mu.data_ptr(), d_L.data_ptr(), d_c.data_ptr(), E, ndim, k, seed, d0, first_ensemble,
                              theta.data_ptr(), lg.data_ptr(), st)
         ctx.logprob_dev(theta.data_ptr(), E * k, lp.data_ptr(), st)
-        if not whole:                                            # (same stream: ordered after the kernels)
+        if order is not None:                                    # the draws as one sample of E ensembles of k rows
+            moved = view.empty((E, k), torch.uint8)
+            _hip.mode_order_dev(theta.data_ptr(), 1, E * k * ndim, E, k, order[0], key_group(order[1]), 0, 0, moved.data_ptr(), st)
+            lp.masked_fill_(moved.bool(), float('-inf'))
+        if not whole:                                           # (same stream: ordered after the kernels)
             logg2[:, d0:d0 + k].copy_(lg)
             logp2[:, d0:d0 + k].copy_(lp)
         view.synchronize()
@@ -495,6 +518,9 @@ def device_evidence(view, logp_view, ctx, n_draws=None, seed=0, neff='ess', prop
     with np.errstate(all='ignore'):
         log_ml = np.log(r.cpu().numpy()) + lstar.cpu().numpy()[0]
         se = np.sqrt(relative_error2(mom.cpu().numpy(), N1, N2, tau))
+    if order is not None:
+        kept = dict(kept, log_symmetry=log_symmetry(order[0]))
+        log_ml = log_ml + kept['log_symmetry']
     return dict(log_ml=log_ml, se=se, iterations=its.cpu().numpy(), n1=N1, n2=N2, neff=ne, tau_f2=tau,
                 frac_outside=outside.cpu().numpy() / float(N2), proposal_mean=np.array(mean), proposal_cov=np.array(cov), **kept)
 
@@ -518,7 +544,17 @@ def _finish(res, bounds, ndim, offset, single):
 class ModelEvidence:
     """Mixin of bisip_amd.utils.utils: the ``chain=`` / ``discard`` / ``thin`` rules are parse_chain's."""
 
-    def get_evidence(self, chain=None, log_prob=None, n_draws=None, seed=0, neff='ess', proposal=None, **kwargs):
+    def _evidence_order(self, order_modes):
+        """``(n_modes, by)`` of ``order_modes=by`` for a model with exchangeable Cole-Cole modes; None for None."""
+        if order_modes is None:
+            return None
+        if not hasattr(self, 'n_modes') or getattr(self, 'model', 'PeltonColeCole') != 'PeltonColeCole':
+            raise ValueError('order_modes belongs to PeltonColeCole: no other model has modes to order')
+        from .modes import _order_argument
+        return _order_argument(order_modes, self.n_modes, self.param_bounds, self.param_names)
+
+    def get_evidence(self, chain=None, log_prob=None, n_draws=None, seed=0, neff='ess', proposal=None, order_modes=None,
+                     **kwargs):
         """The log marginal likelihood of the fit by bridge sampling (bisip_amd.evidence): a dict of ``log_evidence`` (the
         uniform prior normalised), ``log_ml``, its standard error ``se``, ``iterations``, ``n1``, ``n2``, ``neff``, ``tau_f2``,
         ``frac_outside`` (the share of the proposal's draws outside the prior box), ``gaussian_offset``, ``proposal_mean
@@ -528,15 +564,19 @@ class ModelEvidence:
         'mean' ESS of the second half), None (its size) or a number.  ``proposal=(mean, cov)`` replaces the fit: all used
         samples then enter the estimator.  ``discard`` / ``thin`` as for ``get_chain``.  A fit with the device sampler is taken
         on the GPU (``chain='device'``: where the chain lies); a host sampler's, or an explicit unflattened ``chain (n,
-        nwalkers, ndim)`` with its ``log_prob (n, nwalkers)``, in NumPy with ``self.log_prob``."""
+        nwalkers, ndim)`` with its ``log_prob (n, nwalkers)``, in NumPy with ``self.log_prob``.  ``order_modes``:
+        ``'log_tau'``, ``'m'`` or ``'c'`` for a PeltonColeCole model whose modes share one prior box: the estimate is taken
+        over one labelling of the modes (bisip_amd.modes: the samples in order, the draws that are not refused) and
+        ``log_symmetry = log(n_modes!)`` added -- a posterior that mixes the labellings is not bridged by one normal."""
         from .utils import discard_thin, refuse_discard_of_a_chain
         offset = gaussian_offset(self._data['zn_err'])
         bounds = self.param_bounds
+        order = {} if order_modes is None else dict(order=self._evidence_order(order_modes))
         s = self._device_chain_sampler(chain, kwargs)
         if s is not None and s.n_ensembles == 1:
             dt = discard_thin(kwargs)
             res = device_evidence(s.used_samples_dev(**dt), s.log_prob_samples_dev(**dt), s.backend.ctx, n_draws, seed, neff,
-                                  proposal)
+                                  proposal, **order)
             return _finish(res, bounds, s.ndim, offset, True)
         if chain is None:
             self._check_if_fitted()
@@ -546,19 +586,23 @@ class ModelEvidence:
             refuse_discard_of_a_chain(kwargs)
             if log_prob is None:
                 raise ValueError('an explicit chain needs its log-probability: pass log_prob (n, nwalkers)')
-        return bridge_evidence(chain, log_prob, self.log_prob, bounds, n_draws, seed, neff, proposal, offset=float(offset))
+        return bridge_evidence(chain, log_prob, self.log_prob, bounds, n_draws, seed, neff, proposal, offset=float(offset),
+                               **order)
 
 
 class BatchEvidence:
     """Mixin of SpectraBatch (``_fitted()`` is its sampler, ``ctx`` its context)."""
 
-    def get_evidence(self, discard=0, thin=1, n_draws=None, seed=0, neff='ess', proposal=None):
+    _evidence_order = ModelEvidence._evidence_order
+
+    def get_evidence(self, discard=0, thin=1, n_draws=None, seed=0, neff='ess', proposal=None, order_modes=None):
         """The log marginal likelihood of every spectrum's fit by bridge sampling (bisip_amd.evidence): a dict of
         ``log_evidence``, ``log_ml``, ``se``, ``iterations``, ``neff``, ``tau_f2``, ``frac_outside``, ``gaussian_offset``, ``(E,)`` each,
         ``n1``, ``n2``, ``proposal_mean (E, ndim)`` and ``proposal_cov (E, ndim, ndim)``, taken on the device for ``chain='device'``
         and ``'host'`` alike.  Spectrum ``e`` draws from the Philox stream of its survey index.  Under torch.distributed every
-        rank returns its own spectra."""
+        rank returns its own spectra.  ``order_modes`` as the models' ``get_evidence``: PeltonColeCole, the modes in one box."""
         s = self._fitted()
+        order = {} if order_modes is None else dict(order=self._evidence_order(order_modes))
         res = s.evidence(discard=discard, thin=thin, n_draws=n_draws, seed=seed, neff=neff, proposal=proposal,
-                         first_ensemble=self.spectrum_range[0])
+                         first_ensemble=self.spectrum_range[0], **order)
         return _finish(res, self.param_bounds, self.ndim, gaussian_offset(self.zn_err), False)

@@ -18,6 +18,7 @@ import numpy as np
 
 from . import _hip
 from . import decomposition as _decomp
+from . import modes as _modes
 from . import utils as _utils
 from .chainview import ChainView, device_moments, device_percentiles, used_range
 from .interval import DecompositionIntervals
@@ -305,6 +306,29 @@ class Inversion(_plotlib, _utils.utils):
         self._check_if_fitted()
         return self._sampler.get_autocorr_time(**kwargs)
 
+    def _decomposition_samples(self, chain, kwargs):
+        """The samples to summarise, on the device, as a ChainView (bisip_amd.chainview).  The fitted chain with
+        ``discard`` / ``thin`` (where it lies, or an upload of the used samples), or a flat ``chain`` array -- with
+        the rules of get_param_mean (parse_chain)."""
+        import torch
+        ndim = len(self.params)
+        s = self._device_chain_sampler(chain, kwargs)
+        if s is not None:
+            return s.used_samples_dev(**_utils.discard_thin(kwargs))
+        if chain is None:
+            used_range(self.sampler.iteration, **_utils.discard_thin(kwargs))
+        chain = chain if chain is None else np.asarray(chain, dtype=np.float64)
+        flat = np.ascontiguousarray(self.parse_chain(chain, **dict(kwargs)), dtype=np.float64)
+        if flat.ndim != 2 or flat.shape[1] != ndim:
+            raise ValueError(f'the chain must be (n, {ndim}), got {flat.shape}')
+        if flat.shape[0] < 1:
+            raise ValueError('no samples left with ' + ', '.join(f'{k}={v}' for k, v in kwargs.items()))
+        W = self.nwalkers
+        # rows of whole samples (get_chain(flat=True)) keep the sample x walker shape: same bits as the chain itself
+        Wp = W if flat.shape[0] % W == 0 else flat.shape[0]
+        t = torch.from_numpy(flat).to(torch.device('cuda', self.device))
+        return ChainView(t, flat.shape[0] // Wp, 1, Wp, ndim)
+
     # -- properties (reference: src/bisip/models.py:139-179) --------------------------------
     @property
     def p0(self):
@@ -387,29 +411,6 @@ class PolynomialDecomposition(DecompositionIntervals, _decomp.DecompositionRelax
         """``(m_total, log_tau_mean, m_norm)`` of theta (host, INTEGRATING_NAMES): ``(3,)`` or ``(n, 3)``."""
         return _decomp.integrating_params(theta, self.log_tau, self._data['norm_factor'])
 
-    def _decomposition_samples(self, chain, kwargs):
-        """The samples to summarise, on the device, as a ChainView (bisip_amd.chainview).  The fitted chain with
-        ``discard`` / ``thin`` (where it lies, or an upload of the used samples), or a flat ``chain`` array -- with
-        the rules of get_param_mean (parse_chain)."""
-        import torch
-        ndim = len(self.params)
-        s = self._device_chain_sampler(chain, kwargs)
-        if s is not None:
-            return s.used_samples_dev(**_utils.discard_thin(kwargs))
-        if chain is None:
-            used_range(self.sampler.iteration, **_utils.discard_thin(kwargs))
-        chain = chain if chain is None else np.asarray(chain, dtype=np.float64)
-        flat = np.ascontiguousarray(self.parse_chain(chain, **dict(kwargs)), dtype=np.float64)
-        if flat.ndim != 2 or flat.shape[1] != ndim:
-            raise ValueError(f'the chain must be (n, {ndim}), got {flat.shape}')
-        if flat.shape[0] < 1:
-            raise ValueError('no samples left with ' + ', '.join(f'{k}={v}' for k, v in kwargs.items()))
-        W = self.nwalkers
-        # rows of whole samples (get_chain(flat=True)) keep the sample x walker shape: same bits as the chain itself
-        Wp = W if flat.shape[0] % W == 0 else flat.shape[0]
-        t = torch.from_numpy(flat).to(torch.device('cuda', self.device))
-        return ChainView(t, flat.shape[0] // Wp, 1, Wp, ndim)
-
     def _integrating_view(self, chain, kwargs):
         view = self._decomposition_samples(chain, kwargs)
         return view.derived(_decomp.device_integrating_chain(view, self.log_tau, self._data['norm_factor']))
@@ -440,9 +441,9 @@ class PolynomialDecomposition(DecompositionIntervals, _decomp.DecompositionRelax
         return _utils.first_if_scalar(p, out)
 
 
-class PeltonColeCole(Inversion):
+class PeltonColeCole(_modes.ModelModes, Inversion):
     """Generalised (multi-mode) Pelton Cole-Cole model
-    (reference: src/bisip/models.py:232-271).
+    (reference: src/bisip/models.py:232-271).  The modes in order and the per-mode descriptors: bisip_amd.modes.
 
     Args:
         n_modes (int): number of Cole-Cole modes. Defaults to 1.

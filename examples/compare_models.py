@@ -31,6 +31,21 @@ for n_modes in (1, 2):
     dic = model.get_dic(discard=1000)
     print(f'{name}: DIC {dic["dic"]:.1f}, p_D {dic["p_d"]:.1f}; {results[name]["n_high"]} points with p_waic > 0.4')
 
+# the double Cole-Cole model once more with the SAME box for both modes: the chain may now hold both labellings of the modes
+# (here it does: it starts from the ensemble above with the modes of every other walker exchanged), so the evidence is taken
+# over one of them -- the samples with their modes in order of log_tau, log(2!) added (bisip_amd.modes).  Its prior box is 8
+# times the volume of the two boxes above and holds the posterior twice: log_evidence should come out log(8 / 2) = 1.39 lower
+np.random.seed(42)
+model = PeltonColeCole(filepath, nwalkers=64, nsteps=2000, n_modes=2)
+p0 = models['2 modes'].get_chain()[-1].copy()
+p0[1::2] = p0[1::2][:, [0, 2, 1, 4, 3, 6, 5]]
+model.fit(p0=p0, chain='device')
+evidences['2 modes, one box'] = model.get_evidence(discard=1000, order_modes='log_tau')
+rate = model.get_mode_switch_rate(discard=1000)
+print(f'2 modes, one box: {np.mean((rate > 0) & (rate < 1)):.0%} of the walkers switch labels, {np.mean(rate == 1):.0%} keep the other one; '
+      f'ordered log_tau {model.get_ordered_mean(discard=1000)[3:5].round(2)} +- {model.get_ordered_std(discard=1000)[3:5].round(2)}, '
+      f'phase-peak log_tau {model.get_mode_mean(discard=1000)[3:5].round(2)}')
+
 print('model      elpd_waic  p_waic   d_elpd    d_se')
 for row in compare_waic(results):                             # the best model first
     print(f'{row["name"]:<10} {row["elpd_waic"]:9.1f} {row["p_waic"]:7.1f} {row["d_elpd"]:8.1f} {row["d_se"]:7.1f}')

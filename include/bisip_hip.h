@@ -49,7 +49,8 @@ extern "C" {
  *    forward_percentiles_kind and response_moments_dev (+ _workspace) with BISIP_RESPONSE_RI / _PA, then
  *    fit_quality_dev (+ _workspace), then reduced_emulate and ctx_reduced_operands, then q_columns_dev and
  *    loo_columns_dev (+ _workspace), then rtd_descriptors_dev and rtd_descriptors_host, then predictive_check_dev
- *    (+ _workspace) came later under the same number (additions only: a caller that needs them looks the symbols up). */
+ *    (+ _workspace), then mode_order_dev and mode_order_host came later under the same number (additions only: a caller
+ *    that needs them looks the symbols up). */
 #define BISIP_ABI_VERSION 6
 
 /* model_id -- the four reference model classes (src/bisip/models.py:182,232,274,308) */
@@ -441,6 +442,33 @@ int bisip_rtd_descriptors_dev(const double *d_chain, int64_t n_samples, int64_t 
 int bisip_rtd_descriptors_host(const double *chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
                                int64_t walkers_per_ensemble, int ndim, const double *log_tau, int n_tau,
                                const double *q, int n_q, double *out);
+
+/* The modes of every used sample of a PeltonColeCole chain put in order, and the per-mode descriptors of the ordered
+ * row.  A multi-mode Cole-Cole posterior is symmetric under exchange of its modes; ordering them by one parameter group
+ * makes the labelling identifiable.  theta = (r0, m_1..m_K, log_tau_1..K, c_1..K), n_modes = K in 1 ... BISIP_MAX_MODES,
+ * ndim = 1 + 3K.  Chain layout, d_chain / sample_stride conventions as for bisip_chain_moments_dev.  key_group: 0 orders by
+ * m, 1 by log_tau, 2 by c -- ascending by IEEE <, -0.0 and +0.0 tie, every NaN after +inf, NaNs tie, ties keep the stored
+ * order (np.argsort(key, kind='stable')).  Each output is optional (a null pointer: not asked for, no stores); at least
+ * one is required:
+ *   d_ordered (n_samples, n_ensembles*walkers_per_ensemble, 1 + 3K): the row with position j of each group holding the
+ *     values of mode perm[j] -- copies, the bits of the chain;
+ *   d_desc (n_samples, n_ensembles*walkers_per_ensemble, 1 + 2K) = (m_total, log_tau_cc_1..K, log_tau_peak_1..K) of the
+ *     ordered row: m_total = (..(m'_1 + m'_2) + ..) by plain additions, log_tau_cc_j = log_tau'_j + log1p(-m'_j) / c'_j
+ *     (the time constant of the conductivity-form Cole-Cole model, tau (1 - m)^(1/c)), log_tau_peak_j = log_tau'_j +
+ *     log1p(-m'_j) / (2 c'_j) (1/omega at which the phase of mode j alone peaks); IEEE division: -inf or NaN at m = 1, c = 0;
+ *   d_moved (n_samples, n_ensembles*walkers_per_ensemble) bytes: 1 where the order differs from the stored one.
+ * The statement in full: bisip_amd/modes.py.  d_ordered and d_desc are chains that bisip_chain_moments_dev,
+ * bisip_chain_percentiles_dev and bisip_chain_hdi_dev summarise unchanged.  Asynchronous on stream. */
+int bisip_mode_order_dev(const double *d_chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+                         int64_t walkers_per_ensemble, int n_modes, int key_group, double *d_ordered, double *d_desc,
+                         unsigned char *d_moved, void *stream);
+
+/* Host-only, no GPU: the same rows by the same row function (csrc/mode_order.h) on the CPU -- every pointer a host
+ * pointer -- which is what tests/test_gpu_modes.py holds bisip_mode_order_dev to: bit for bit on ordered, moved and m_total
+ * (log1p is the host's here and the device's there). */
+int bisip_mode_order_host(const double *chain, int64_t n_samples, int64_t sample_stride, int64_t n_ensembles,
+                          int64_t walkers_per_ensemble, int n_modes, int key_group, double *ordered, double *desc,
+                          unsigned char *moved);
 
 /* The shapes of the posterior of a chain resident in device memory: the counts the reference draws in
  * plot_histograms (src/bisip/plotlib.py:56-90: np.histogram of every parameter, bins = 25) and in plot_corner
