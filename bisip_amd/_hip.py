@@ -198,6 +198,12 @@ SYMBOLS = {
     'bisip_predictive_check_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                                   ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    'bisip_gauss_newton_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] +
+                               [ctypes.c_void_p] * 4),
+    'bisip_map_fit_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                         ctypes.c_int64, ctypes.c_double] + [ctypes.c_void_p] * 8),
+    'bisip_lm_step_host': (ctypes.c_int, [ctypes.c_int, _dp, _dp, _dp, _dp, _dp, ctypes.c_double, _dp, _dp, _dp,
+                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]),
     'bisip_columns_percentiles_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int,
                                                      ctypes.c_void_p, ctypes.c_void_p]),
     'bisip_q_columns_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
@@ -803,6 +809,23 @@ class HipContext:
                                                     d_pit_ptr or None, d_row_ptr or None, d_sign_changes_ptr or None,
                                                     d_work_ptr or None, int(work_bytes), ctypes.c_void_p(stream)))
 
+    def gauss_newton_dev(self, first_spectrum, n_spectra, d_theta_ptr, S, d_chi2_ptr, d_g_ptr, d_A_ptr, stream=0):
+        """The normal equations of the misfit (bisip_amd.mapfit.normal_equations) at ``S`` points for each of ``n_spectra``
+        spectra, d_theta (n_spectra, S, ndim): d_chi2 (n_spectra, S), d_g (n_spectra, S, ndim), d_A (n_spectra, S, ndim,
+        ndim), any 0 / None.  Device pointers (ints), asynchronous on ``stream``."""
+        _check(self._lib.bisip_gauss_newton_dev(self._h, int(first_spectrum), int(n_spectra), d_theta_ptr or None, int(S),
+                                                d_chi2_ptr or None, d_g_ptr or None, d_A_ptr or None, ctypes.c_void_p(stream)))
+
+    def map_fit_dev(self, first_spectrum, n_spectra, d_starts_ptr, S, max_iter, pred_tol, d_theta_ptr, d_chi2_ptr, d_logp_ptr,
+                    d_pred_ptr, d_A_ptr, d_iterations_ptr, d_status_ptr, stream=0):
+        """The Levenberg-Marquardt loop of bisip_amd.mapfit.lm_fit from ``S`` starts for each of ``n_spectra`` spectra,
+        d_starts (n_spectra, S, ndim), in one launch: per (spectrum, start) d_theta (ndim), d_chi2, d_logp, d_pred, d_A
+        (ndim, ndim), d_iterations and d_status (int64), any 0 / None.  Device pointers (ints), asynchronous on ``stream``."""
+        _check(self._lib.bisip_map_fit_dev(self._h, int(first_spectrum), int(n_spectra), d_starts_ptr or None, int(S),
+                                           int(max_iter), float(pred_tol), d_theta_ptr or None, d_chi2_ptr or None,
+                                           d_logp_ptr or None, d_pred_ptr or None, d_A_ptr or None, d_iterations_ptr or None,
+                                           d_status_ptr or None, ctypes.c_void_p(stream)))
+
     def q_columns_dev(self, first_spectrum, n_spectra, d_cols_ptr, rows_per_spectrum, stream=0):
         """The Re / Im columns ``(n_spectra, 2N, rows_per_spectrum)`` that forward_columns_dev wrote become, in place, the
         squared standardised residuals ``q = (y - Z)^2 * iv`` of their data points (the bits of fitquality.pointwise_q).
@@ -1015,6 +1038,24 @@ def mode_order_host(chain, n_samples, sample_stride, n_ensembles, walkers_per_en
                                                 int(key_group), None if o is None else _p(o), None if d is None else _p(d),
                                                 None if mv is None else mv.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte))))
     return o, d, None if mv is None else mv.astype(bool)
+
+
+def lm_step_host(A, g, theta, bounds, lam):
+    """Host-only, no GPU: the dense step of one Levenberg-Marquardt iteration by the functions the kernel calls
+    (bisip_lm_step_host, csrc/lm_step.h).  A (ndim, ndim), g, theta (ndim), bounds (2, ndim) the PRIOR box.  Returns a dict:
+    fixed (ndim,) bool, pred, ok, and delta, trial (ndim) of the candidate with this lambda (NaN when not ok)."""
+    A, g, theta = _c(A), _c(g).ravel(), _c(theta).ravel()
+    b = _c(bounds).reshape(2, -1)
+    lo, hi = _c(b[0]), _c(b[1])
+    n = theta.size
+    if A.shape != (n, n) or g.size != n or lo.size != n:
+        raise ValueError(f'A ({n}, {n}), g, theta ({n},) and bounds (2, {n}) expected')
+    delta, trial, pred = np.empty(n), np.empty(n), np.empty(1)
+    fixed, ok = ctypes.c_int64(0), ctypes.c_int(0)
+    _check(load_library().bisip_lm_step_host(n, _p(A), _p(g), _p(theta), _p(lo), _p(hi), float(lam), _p(delta), _p(trial),
+                                             _p(pred), ctypes.byref(fixed), ctypes.byref(ok)))
+    return dict(fixed=np.array([(fixed.value >> j) & 1 for j in range(n)], dtype=bool), pred=float(pred[0]), ok=bool(ok.value),
+                delta=delta, trial=trial)
 
 
 def chain_range_dev(d_chain_ptr, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, d_out_ptr,

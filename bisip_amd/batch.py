@@ -18,6 +18,7 @@ from .fitquality import BatchFitQuality
 from .interval import BatchIntervals
 from .dist import shard_range
 from .loo import BatchLoo
+from .mapfit import BatchMapFit
 from .modes import BatchModes
 from .predictive import BatchPredictive
 from .evidence import BatchEvidence
@@ -57,7 +58,7 @@ def default_params(model, n_modes=1, poly_deg=5):
 
 
 class SpectraBatch(BatchCovariance, BatchIntervals, BatchEss, BatchDiagnostics, BatchResponse, BatchFitQuality, BatchLoo,
-                   BatchEvidence, BatchPredictive, decomposition.BatchRelaxation, BatchModes):
+                   BatchEvidence, BatchPredictive, decomposition.BatchRelaxation, BatchModes, BatchMapFit):
     """E spectra inverted together with the same model class.
 
     Args:
@@ -137,10 +138,19 @@ class SpectraBatch(BatchCovariance, BatchIntervals, BatchEss, BatchDiagnostics, 
         ``get_param_std`` then summarise them on the device and ``get_chain`` copies them to
         the host only when called.  ``persistent``: one workgroup per spectrum runs all
         iterations of a chunk in one launch (same chain; default: when the ensembles fit a
-        workgroup and the batch fills the chip, see DeviceEnsembleSampler)."""
+        workgroup and the batch fills the chip, see DeviceEnsembleSampler).  ``p0='map'``: ``fit_map()`` finds every
+        spectrum's least-squares optimum first (32 starts each, one launch) and the walkers are drawn in a ball of its Laplace
+        covariance around it (``mapfit.ball``).  The starts (a RandomState(0)) and one seed per spectrum for its ball (from the
+        global NumPy RNG) are drawn for the whole survey and this rank's block kept, so a spectrum's chain does not depend on
+        the number of ranks, as with ``p0=None``; ``get_map()`` returns the optima."""
         if chain not in ('host', 'device'):
             raise ValueError("chain must be 'host' or 'device'")
         E, Wp, ndim = self.n_spectra, self.nwalkers, self.ndim
+        if isinstance(p0, str):
+            # every spectrum's least-squares optimum first (fit_map), the walkers in a ball around it (mapfit.ball)
+            if p0 != 'map':
+                raise ValueError("p0 must be None, an array (n_spectra, nwalkers, ndim) or 'map'")
+            p0 = self._map_walkers(np.random)
         if p0 is None:
             # the whole survey's starts from the global RNG, this rank's block kept: with the same
             # np.random.seed on every rank a spectrum starts (and runs) the same on any number of GPUs

@@ -194,7 +194,10 @@ class Inversion(_plotlib, _utils.utils):
 
         Args:
             p0 (ndarray): starting positions (nwalkers, ndim); drawn uniformly from the
-                prior box with the global NumPy RNG when None.
+                prior box with the global NumPy RNG when None.  'map': ``fit_map()`` finds the least-squares
+                optimum first (32 starts from a RandomState(0) of its own) and the walkers are drawn in a ball of
+                its Laplace covariance around it (``mapfit.ball``, from the global NumPy RNG), which saves the
+                burn-in; ``get_map()`` returns the optimum.
             pool: accepted for signature compatibility and ignored: the reference hands it to
                 emcee to spread the per-walker Python calls over processes
                 (src/bisip/models.py:91-94,115); here a whole half-ensemble is one kernel launch.
@@ -224,6 +227,10 @@ class Inversion(_plotlib, _utils.utils):
                 one compute unit still beats launches spread over the chip (256-1024 walkers
                 depending on the model, HipContext.persistent_walkers).
         """
+        if isinstance(p0, str):
+            if p0 != 'map':
+                raise ValueError("p0 must be None, an array (nwalkers, ndim) or 'map'")
+            p0 = self._map_walkers(np.random)
         self._p0 = p0
         self.ndim = self.param_bounds.shape[1]
         if self._p0 is None:

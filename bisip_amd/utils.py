@@ -19,6 +19,7 @@ from .ess import ModelEss
 from .fitquality import ModelFitQuality
 from .interval import ModelIntervals
 from .loo import ModelLoo
+from .mapfit import ModelMapFit
 from .predictive import ModelPredictive
 from .evidence import ModelEvidence
 from .response import ModelResponse
@@ -189,7 +190,7 @@ def refuse_discard_of_a_chain(kwargs):
 
 
 class utils(ModelCovariance, ModelIntervals, ModelEss, ModelDiagnostics, ModelResponse, ModelFitQuality, ModelLoo,
-            ModelEvidence, ModelPredictive):
+            ModelEvidence, ModelPredictive, ModelMapFit):
     """Mixin with the reference's utility methods (src/bisip/utils.py:15); the posterior covariance, correlation and best
     sample come from bisip_amd.covariance.ModelCovariance, the highest-density intervals from
     bisip_amd.interval.ModelIntervals, the effective sample sizes from bisip_amd.ess.ModelEss, the rank-normalised R-hat
@@ -197,7 +198,8 @@ class utils(ModelCovariance, ModelIntervals, ModelEss, ModelDiagnostics, ModelRe
     the model response from bisip_amd.response.ModelResponse, WAIC, DIC and the per-point misfit
     from bisip_amd.fitquality.ModelFitQuality, PSIS-LOO and the Pareto k of every point from bisip_amd.loo.ModelLoo,
     the log marginal likelihood by bridge sampling from bisip_amd.evidence.ModelEvidence, the posterior predictive checks
-    from bisip_amd.predictive.ModelPredictive."""
+    from bisip_amd.predictive.ModelPredictive, the Levenberg-Marquardt MAP fit before any chain from
+    bisip_amd.mapfit.ModelMapFit."""
 
     def load_data(self, filename, headers=1, ph_units='mrad'):
         return load_data(filename, headers, ph_units)

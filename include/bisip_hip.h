@@ -49,8 +49,8 @@ extern "C" {
  *    forward_percentiles_kind and response_moments_dev (+ _workspace) with BISIP_RESPONSE_RI / _PA, then
  *    fit_quality_dev (+ _workspace), then reduced_emulate and ctx_reduced_operands, then q_columns_dev and
  *    loo_columns_dev (+ _workspace), then rtd_descriptors_dev and rtd_descriptors_host, then predictive_check_dev
- *    (+ _workspace), then mode_order_dev and mode_order_host came later under the same number (additions only: a caller
- *    that needs them looks the symbols up). */
+ *    (+ _workspace), then mode_order_dev and mode_order_host, then gauss_newton_dev, map_fit_dev and lm_step_host came
+ *    later under the same number (additions only: a caller that needs them looks the symbols up). */
 #define BISIP_ABI_VERSION 6
 
 /* model_id -- the four reference model classes (src/bisip/models.py:182,232,274,308) */
@@ -821,6 +821,48 @@ int64_t bisip_predictive_check_workspace(bisip_ctx *ctx, int64_t n_samples, int6
 int bisip_predictive_check_dev(bisip_ctx *ctx, int64_t first_spectrum, int64_t n_spectra, const double *d_chain,
                                int64_t n_samples, int64_t sample_stride, int64_t walkers_per_ensemble, double *d_pit,
                                double *d_row, long long *d_sign_changes, void *d_work, int64_t work_bytes, void *stream);
+
+/* The maximum a posteriori point before any chain exists: a multi-start Levenberg-Marquardt fit of the Gaussian misfit
+ * inside the prior box, with a central-difference Jacobian (bisip_amd/mapfit.py holds the definitions: normal_equations,
+ * lm_fit; csrc/lm_step.h the dense step).  The context's box must be finite (BISIP_EINVAL otherwise).  Per parameter j,
+ * range_j = hi_j - lo_j: the stencil step is h_j = 1e-6 range_j and the inner box [lo_j + h_j, hi_j - h_j].
+ *
+ * bisip_gauss_newton_dev: the normal equations at S given points for each of n_spectra consecutive spectra starting with
+ * first_spectrum, d_theta (n_spectra, S, ndim), taken as they are (not clipped).  y and iv = 1 / sigma^2 from the
+ * frequency's record as for bisip_fit_quality_dev, Z the bits of bisip_forward:
+ *   d = y - Z(theta);  dZ_j = (Z(theta + h_j e_j) - Z(theta - h_j e_j)) / (2 h_j);
+ *   d_chi2 (n_spectra, S) = sum (d d) iv;  d_g (n_spectra, S, ndim): g_j = -sum (dZ_j d) iv;
+ *   d_A (n_spectra, S, ndim, ndim): A_jk = sum (dZ_j dZ_k) iv;
+ * every sum over the frequencies in ascending order, the real part before the imaginary one, from 0.0, every product and
+ * sum rounded on its own (no fma): the bits of mapfit.ordered_normal_equations from bisip_forward's responses at the
+ * 2 ndim + 1 stencil points.  A point with a parameter that is not finite gives NaN in its outputs and leaves the other
+ * points alone.  Any output may be null (no stores).  n_spectra * S < 2^31.  Asynchronous on stream.
+ *
+ * bisip_map_fit_dev: the whole loop of mapfit.lm_fit from S starts per spectrum, d_starts (n_spectra, S, ndim), each
+ * clipped into the inner box first; one launch, no host round trip.  lambda starts at 1e-3.  One iteration at theta:
+ * the normal equations; parameter j is FIXED when theta_j is on the inner lower bound with g_j > 0 or on the inner upper
+ * bound with g_j < 0, or when A_jj is 0 (its row, column and g_j are 0 then and its step is 0 either way), every other
+ * is free; D = diag(A_ff) (no entry of it is 0, by the rule before); pred = g_f' A_ff^-1 g_f / 2 by Cholesky in the order csrc/lm_step.h
+ * states (+inf when A_ff is not positive definite); status 0 (converged) when pred <= pred_tol; status 2 (cap) when
+ * max_iter iterations are done (0 <= max_iter <= 1000); else the candidates lambda, 10 lambda, ..., at most 12, each
+ * clip(theta + delta) onto the inner box with (A_ff + lambda D) delta = -g_f by Cholesky (a failed factorisation is a
+ * rejected candidate); the first whose chi2 is finite and strictly lower becomes theta and lambda = max(its lambda / 10,
+ * 1e-12); status 1 (stalled) when none is.  Outputs, per (spectrum, start), any may be null: d_theta (., ndim) the
+ * result; d_chi2; d_logp = -chi2 / 2 + the spectrum's constant (-sum ln sigma^2), the log-probability there; d_pred;
+ * d_A (., ndim, ndim) the Gauss-Newton Hessian there; d_iterations, d_status int64.  A start's result depends on nothing
+ * but the start.  A start with a NaN ends stalled with NaN in theta and chi2.  Asynchronous on stream. */
+int bisip_gauss_newton_dev(bisip_ctx *ctx, int64_t first_spectrum, int64_t n_spectra, const double *d_theta, int64_t S,
+                           double *d_chi2, double *d_g, double *d_A, void *stream);
+int bisip_map_fit_dev(bisip_ctx *ctx, int64_t first_spectrum, int64_t n_spectra, const double *d_starts, int64_t S,
+                      int64_t max_iter, double pred_tol, double *d_theta, double *d_chi2, double *d_logp, double *d_pred,
+                      double *d_A, int64_t *d_iterations, int64_t *d_status, void *stream);
+
+/* Host-only, no GPU: the dense step of one iteration by the functions the kernel calls (csrc/lm_step.h), every pointer a
+ * host pointer.  A (ndim, ndim), g, theta, lo, hi (ndim; the PRIOR box, the inner box is taken from it), 1 <= ndim <= 16.
+ * fixed: bit j set where parameter j is fixed; pred as above; delta and trial (ndim) of the candidate with this lambda
+ * (lambda <= 0: the undamped system), NaN when its factorisation failed, *ok = 0 then.  Any output may be null. */
+int bisip_lm_step_host(int ndim, const double *A, const double *g, const double *theta, const double *lo, const double *hi,
+                       double lambda, double *delta, double *trial, double *pred, int64_t *fixed, int *ok);
 
 /* PSIS-LOO, step 1: the Re / Im columns that bisip_forward_columns_dev wrote for n_spectra consecutive spectra starting
  * with first_spectrum -- d_cols (n_spectra, 2N, rows_per_spectrum) -- become, where they lie, the squared standardised
