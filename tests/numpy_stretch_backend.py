@@ -1,7 +1,13 @@
 """CPU stand-in for bisip_amd.sampler.HipStretchBackend, used ONLY by tests to run the
 multi-rank driver logic of DeviceEnsembleSampler over gloo.  Implements the semantics
 of bisip_stretch_{half,eval,apply}_dev (include/bisip_hip.h) in NumPy on CPU tensors,
-with the oracle as the log-probability."""
+with the oracle as the log-probability.
+
+``philox_stream`` and ``NumpyStretchBackend._slot`` together are THE statement of the rng='philox' contract: every
+device path is held to them bit for bit.  That the contract itself samples the right law -- the exponent of z, the
+density g(z) ~ 1/sqrt(z), the partner from the other half, the strict acceptance at a prior face -- is what
+tests/exact_posterior.py calibrates: tests/test_exact_posterior.py holds this statement, and
+tests/test_gpu_exact_posterior.py the kernels, to a posterior that is drawn exactly."""
 
 import numpy as np
 import torch
@@ -37,26 +43,26 @@ def philox_stream(W, ndim, a, seed, step0, perm, E=1, e0=0):
     out = dict(active=np.zeros((n, 2, E, nh), np.int32), partner=np.zeros((n, 2, E, nh), np.int32),
                zz=np.ones((n, 2, E, nh)), factor=np.zeros((n, 2, E, nh)), logu=np.zeros((n, 2, E, nh)))
     k0, k1 = seed & 0xffffffff, seed >> 32
+    es = np.arange(E, dtype=np.int64)[:, None]          # every ensemble at once: the same words, element by element
     for k in range(n):
         A, Ainv, B = [int(x) for x in perm[k]]
         for h in (0, 1):
             Ns = nh if h == 0 else W // 2
             Nc = W // 2 if h == 0 else nh
-            t = np.arange(Ns, dtype=np.uint64)
+            t = np.arange(Ns, dtype=np.uint64)[None, :]
             ti = t.astype(np.int64)
-            for e in range(E):
-                c2 = h | ((e0 + e) << 1)
-                x0, x1, x2, _ = philox4x32_10(t, step0 + k, c2, 0, k0, k1)
-                y0, y1, _, _ = philox4x32_10(t, step0 + k, c2, 1, k0, k1)
-                r = ((x2 * np.uint64(Nc)) >> np.uint64(32)).astype(np.int64)
-                v = (a - 1.0) * u53(x0, x1) + 1.0
-                z = (v * v) / a
-                out['active'][k, h, e, :Ns] = e * W + (Ainv * ((2 * ti + h - B) % W)) % W
-                out['partner'][k, h, e, :Ns] = e * W + (Ainv * ((2 * r + (1 - h) - B) % W)) % W
-                out['zz'][k, h, e, :Ns] = z
-                out['factor'][k, h, e, :Ns] = (ndim - 1.0) * np.log(z)
-                with np.errstate(divide='ignore'):
-                    out['logu'][k, h, e, :Ns] = np.log(u53(y0, y1))
+            c2 = h | ((e0 + es) << 1)
+            x0, x1, x2, _ = philox4x32_10(t, step0 + k, c2, 0, k0, k1)
+            y0, y1, _, _ = philox4x32_10(t, step0 + k, c2, 1, k0, k1)
+            r = ((x2 * np.uint64(Nc)) >> np.uint64(32)).astype(np.int64)
+            v = (a - 1.0) * u53(x0, x1) + 1.0
+            z = (v * v) / a
+            out['active'][k, h, :, :Ns] = es * W + (Ainv * ((2 * ti + h - B) % W)) % W
+            out['partner'][k, h, :, :Ns] = es * W + (Ainv * ((2 * r + (1 - h) - B) % W)) % W
+            out['zz'][k, h, :, :Ns] = z
+            out['factor'][k, h, :, :Ns] = (ndim - 1.0) * np.log(z)
+            with np.errstate(divide='ignore'):
+                out['logu'][k, h, :, :Ns] = np.log(u53(y0, y1))
     return {name: arr.reshape(n, 2, E * nh) for name, arr in out.items()}
 
 
