@@ -319,7 +319,38 @@ def table_guard():
                      'checks', 'rows measured', 'worst relative error seen (tolerance 2e-11)'])
 
 
+def table_row_pass():
+    """Medians of the fused passes over a chain on the parent's build, the build with row_pass.h and the parent's again; the
+    margin is the largest (max - min) / median of a parent run's repeats ((median - best) / median where none are kept)."""
+    runs = ('parent1', 'refactor', 'parent2')
+    calls = (('response', 'moments_ri_ms', 'best', 'moments RI (`k_response_moments`)'), ('response', 'moments_pa_ms', 'best', 'moments PA'),
+             ('fit_quality', 'fit_ms', 'repeats', 'fit (`k_fit_quality`)'), ('fit_quality', 'moments_ri_ms', 'repeats', 'moments RI'),
+             ('predictive', 'predictive_ms', 'spread', 'all outputs'), ('predictive', 'predictive_rows_ms', 'spread', 'rows (`k_pred_rows`)'),
+             ('predictive', 'predictive_pit_ms', 'spread', 'pit (`k_pred_rows` + `k_pred_points`)'), ('predictive', 'fit_ms', 'spread', 'fit'))
+
+    def spread(d, key, how):
+        if how == 'spread':
+            return d[key[:-2] + 'spread']
+        if how == 'best':
+            return (d[key] - d[key + '_best']) / d[key]
+        v = sorted(d[key + '_repeats'])
+        return (v[-1] - v[0]) / v[len(v) // 2]
+
+    rows = []
+    for bench, key, how, what in calls:
+        data = {r: jlines(f'row_pass_{r}_{bench}_bench.jsonl') for r in runs}
+        cells = [' \\| '.join(f'{d[key]:.3f}' for d in data[r]) for r in runs]
+        margin = [max(spread(data[r][i], key, how) for r in ('parent1', 'parent2')) for i in range(len(data['parent1']))]
+        parent = [(data['parent1'][i][key] + data['parent2'][i][key]) / 2 for i in range(len(margin))]
+        over = [data['refactor'][i][key] / parent[i] - 1 for i in range(len(margin))]
+        rows.append([bench, what] + cells + [' \\| '.join(f'{100 * x:+.1f} %' for x in over), ' \\| '.join(f'{100 * x:.1f} %' for x in margin),
+                                              'yes' if all(o <= m for o, m in zip(over, margin)) else 'NO'])
+    return md(rows, ['bench', 'call, ms: double Cole-Cole \\| PolynomialDecomposition degree 5', 'parent', 'refactor', 'parent again',
+                     'refactor over the parent runs\' mean', 'margin', 'within'])
+
+
 TABLES = {
+    'row_pass': table_row_pass,
     'group_sampler': table_group_sampler, 'big_ensemble': table_big_ensemble, 'guard': table_guard,
     'bench': table_bench, 'variants': table_variants, 'sweep': table_sweep, 'forward': table_forward,
     'host_path': table_host_path, 'samplers': table_samplers, 'cfg4': table_cfg4, 'cfg5': table_cfg5,
@@ -386,6 +417,7 @@ FILES = [
     (rn('micro_fp64_stream_ceiling.txt'), '`benchmarks/micro/fp64_stream_ceiling 0.5` (hipcc from `fp64_stream_ceiling.hip`)', 'round 5: what a stream of independent fp64 FMAs reaches (0.82-0.89 of the nominal issue peak with full-mantissa operands, the waves at 2.2-2.3 GHz; 0.87-0.94 on small integers): the ceiling `bench.py` measures in every run (`fp64_fma_stream`)'),
     (rn('micro_fma_operands.txt'), '`benchmarks/micro/fma_operands` (hipcc from `fma_operands.hip`)', 'round 5: a fp64 FMA with three vector sources costs 2-4 % more issue time than one with a scalar source, whatever the banks: not what holds Dias2000 back'),
     (rn('micro_host_pipeline.txt'), 'a scratch experiment with chunk size, staging and thread count as knobs', 'round 5: the host-buffer entry is bound by the host copy out of pageable memory (54 GB/s from a cache-resident 64 MB source, 37-41 GB/s from DRAM at 256 MB however it is staged or overlapped)'),
+    ('row_pass_parent1_*_bench.jsonl, row_pass_refactor_*_bench.jsonl, row_pass_parent2_*_bench.jsonl', '`python benchmarks/response_bench.py --only moments --out DIR`, `fit_quality_bench.py --out DIR`, `predictive_bench.py --out DIR`: the library of the commit before `row_pass.h`, the one with it, and the first again, in one session on one box', 'the fused passes over a chain before and after their kernels moved onto one row walk (DESIGN.md 3.12): every median within the spread of the parent\'s repeats'),
     (rn('micro_post_run_stall.txt'), '`python benchmarks/micro/post_run_stall.py kernel`, `upload_cost.py plain`', 'the sporadic 20-30 ms delay of the first device work after a synchronisation early in a process'),
 ]
 

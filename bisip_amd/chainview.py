@@ -10,7 +10,7 @@ bisip_chain_percentiles_dev); the others are in bisip_amd.autocorr, bisip_amd.hi
 
 import numpy as np
 
-__all__ = ('used_range', 'ChainView', 'device_moments', 'device_percentiles', 'moment_splits', 'ordered_sweep',
+__all__ = ('used_range', 'ChainView', 'host_chain_view', 'device_moments', 'device_percentiles', 'moment_splits', 'ordered_sweep',
            'ordered_moments')
 
 
@@ -99,6 +99,18 @@ class ChainView:
         t = self.tensor
         return torch.as_strided(t, (self.n, self.n_ensembles * self.walkers_per_ensemble, self.ndim),
                                 (self.stride, self.ndim, 1), t.storage_offset() + self.offset)
+
+
+def host_chain_view(flat, ctx):
+    """The view of a host chain ``(n, ndim)`` of the model of ``ctx`` (a HipContext) as one ensemble of one walker.  The
+    chain goes up once, to the context's device; its rows are the rows of get_chain(flat=True), so that a pass over the
+    view takes the same sums in the same order as one over the chain where a sampler left it."""
+    import torch
+    flat = np.ascontiguousarray(flat, dtype=np.float64)
+    if flat.ndim != 2 or flat.shape[1] != ctx.ndim or flat.shape[0] < 1:
+        raise ValueError(f'the chain must be (n, {ctx.ndim}), n >= 1, got {flat.shape}')
+    t = torch.from_numpy(flat).to(torch.device('cuda', ctx.device))
+    return ChainView(t, flat.shape[0], 1, 1, ctx.ndim)
 
 
 class _DeviceSlabs:

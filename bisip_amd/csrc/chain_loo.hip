@@ -31,10 +31,10 @@
 // Resource report (-Rpass-analysis=kernel-resource-usage, gfx950): 6 to 94 VGPRs, no AGPRs and no scratch in any kernel of
 // the unit; the table stands before the kernels.
 //
-// The unit needs the context (the records of bisip_q_columns_dev) and so takes host.h through response_plan.h, as
+// The unit needs the context (the records of bisip_q_columns_dev) and so takes host.h through row_pass.h, as
 // dispatch_fit.hip does; kernels.h and chain.h both define wave_sum, so what it uses of the column toolkit (chain.h,
 // chain_columns.hip) is declared here instead of included.
-#include "response_plan.h"
+#include "row_pass.h"
 
 namespace bisip {
 namespace host {

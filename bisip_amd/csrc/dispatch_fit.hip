@@ -6,13 +6,10 @@
 // fit_sums); fitquality.ordered_fit_sums restates the order of every sum below in NumPy: the same bits of mean_q and var_q
 // from the same responses, and the same order of lmeh with NumPy's exp.
 //
-// Rows, plan (rm_plan of response_plan.h; response.plan), row slots, segments: those of dispatch_response.hip.  A
-// workgroup of 256 threads takes one (spectrum, segment); row i of a segment goes to slot i mod 256; a slot takes its rows
-// in ascending order.
+// Rows, plan, row slots, wave order, segments: row_pass.h.
 //
-//   * q.  rec[0..3] = y_re, y_im, 1/s2_re, 1/s2_im of the frequency's record; Z = M::eval, the bits of forward();
-//     d = y - Z;  t = d * d;  q = t * iv, each rounded on its own (no fma).  A row with a parameter that is not finite
-//     counts as q = NaN at every point.
+//   * q = q_of_record of Z = M::eval, the bits of forward().  A row with a parameter that is not finite counts as q = NaN
+//     at every point.
 //   * Four states per (part, frequency) and lane -- S, P, m, s -- against the response kernel's two, so the frequencies go
 //     in tiles of FQ_JT = 4: 32 doubles of state per lane, the chain is read again for every tile (from L2 / MALL after
 //     the first), and no output depends on the tiling.  Resource report (-Rpass-analysis=kernel-resource-usage, gfx950):
@@ -24,12 +21,11 @@
 //     s = s + exp(-(q - m) / 2).  A row q < m: s = s * exp(-(m - q) / 2) + 1, m = q (product and sum rounded on their own).
 //     One exp (the device library's) per row.  Two pairs merge to m' = min(m_a, m_b); the side whose m is larger is scaled
 //     by exp(-(m - m') / 2), the other (both, when the minima are equal) is not; s' = s_a + s_b.
-//   * The 256 slots are added / merged pairwise within each wave of 64 slots, 32, 16, ..., 1 apart; the four waves'
-//     results then in ascending order ((w0 + w1) + w2) + w3.
-//   * Segments in ascending order (...((s_0 + s_1) + s_2) ...) by k_fit_merge (nseg > 1).
+//   * The pairs of the 256 slots and of the segments are merged in the order of the sums, the segments by k_fit_merge
+//     (nseg > 1).
 //   * mean_q = c + S / R;  var_q = (P - (S * S) / R) / (R - 1), < 0 becomes 0 (a NaN stays; R = 1 gives NaN);
 //     lmeh = -m / 2 + log(s / R).
-#include "response_plan.h"
+#include "row_pass.h"
 
 using namespace bisip;
 using namespace bisip::host;
@@ -38,26 +34,11 @@ namespace {
 
 constexpr int FQ_JT = 4;                      // frequencies per tile: 8 * FQ_JT doubles of state per lane
 
-struct FqArgs {
-    const double *chain;         // walker 0 of the call's first spectrum in the first used sample
-    long long stride, R, seg_rows, nseg;
-    int Wp, N;
-    const double *cb;            // records of the call's first spectrum
-    long long cb_stride;
+struct FqArgs : RowPass {
     double *mean_q, *var_q, *lmeh;   // (n_spectra, 2, N) each; any may be null
     double *part;                // (n_spectra, nseg, 8N): S, P, m, s of the 2N points each (nseg > 1)
     double *shift;               // (n_spectra, 2N): c, written by segment 0 (nseg > 1)
 };
-
-// q of both parts of one frequency from the response (zr, zi) and the record's data and weights
-__device__ __forceinline__ void fq_q(const double *rec, double zr, double zi, double &q0, double &q1)
-{
-    typedef const double __attribute__((address_space(4))) *const_ptr;   // scalar loads, as eval_const
-    const const_ptr r = (const_ptr)rec;
-    const double d0 = __dsub_rn(r[0], zr), d1 = __dsub_rn(r[1], zi);
-    q0 = __dmul_rn(__dmul_rn(d0, d0), r[2]);
-    q1 = __dmul_rn(__dmul_rn(d1, d1), r[3]);
-}
 
 __device__ __forceinline__ double fq_scale(double d) { return exp(__dmul_rn(-0.5, d)); }
 
@@ -100,31 +81,22 @@ __global__ __launch_bounds__(RM_THREADS) void k_fit_quality(const FqArgs a)
     __shared__ double s_wave[4][NV];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int N = a.N, Wp = a.Wp;
-    const long long e = blockIdx.x / a.nseg, g = blockIdx.x - e * a.nseg;
-    const long long r0 = g * a.seg_rows;
-    const int R = (int)(a.R - r0 < a.seg_rows ? a.R - r0 : a.seg_rows);
-    const double *__restrict__ base = a.chain + e * Wp * NDIM;      // walker 0 of the spectrum in the first used sample
-    const double *__restrict__ cb = a.cb + e * a.cb_stride;
+    const int N = a.N;
+    RowCursor<NDIM> at(a, blockIdx.x, tid);
+    const long long e = at.e, g = at.g;
+    const double *__restrict__ cb = at.cb;
 
     double th0[NDIM];
 #pragma unroll
-    for (int q = 0; q < NDIM; ++q) th0[q] = base[q];
+    for (int q = 0; q < NDIM; ++q) th0[q] = at.base[q];
     const typename M::Setup s0 = M::setup(th0);
-
-    // this thread's first row: sample k0, walker w0; from one of its rows to the next
-    const long long k0 = (r0 + tid) / Wp;
-    const int w0 = (int)(r0 + tid - k0 * Wp);
-    const int step_k = RM_THREADS / Wp, step_w = RM_THREADS - step_k * Wp;
 
     for (int j0 = 0; j0 < N; j0 += JT) {
         if (tid < JT && j0 + tid < N) {                             // the shift of this tile's points
             const double *rec = cb + (long long)(j0 + tid) * M::REC;
             double z0, z1, c0, c1;
             M::eval(s0, rec + 4, z0, z1);
-            const double d0 = __dsub_rn(rec[0], z0), d1 = __dsub_rn(rec[1], z1);
-            c0 = __dmul_rn(__dmul_rn(d0, d0), rec[2]);
-            c1 = __dmul_rn(__dmul_rn(d1, d1), rec[3]);
+            q_of_record(rec, z0, z1, c0, c1);
             s_c[tid] = c0;
             s_c[JT + tid] = c1;
         }
@@ -135,18 +107,11 @@ __global__ __launch_bounds__(RM_THREADS) void k_fit_quality(const FqArgs a)
             S[0][jj] = S[1][jj] = P[0][jj] = P[1][jj] = Sx[0][jj] = Sx[1][jj] = 0.0;
             Mn[0][jj] = Mn[1][jj] = HUGE_VAL;
         }
-        long long k = k0;
-        int w = w0;
+        at.rewind();
 #pragma unroll 1
-        for (int i = tid; i < R; i += RM_THREADS) {
-            const double *__restrict__ row = base + k * a.stride + (long long)w * NDIM;
+        for (int i = tid; i < at.R; i += RM_THREADS) {
             double th[NDIM];
-            bool bad = false;
-#pragma unroll
-            for (int q = 0; q < NDIM; ++q) {
-                th[q] = row[q];
-                bad |= !(fabs(th[q]) < HUGE_VAL);                   // NaN or +-inf
-            }
+            const bool bad = load_row<NDIM>(at.row(), th);
             const typename M::Setup s = M::setup(th);
 #pragma unroll
             for (int jj = 0; jj < JT; ++jj) {
@@ -154,7 +119,7 @@ __global__ __launch_bounds__(RM_THREADS) void k_fit_quality(const FqArgs a)
                     const double *rec = cb + (long long)(j0 + jj) * M::REC;
                     double z0, z1, q0, q1;
                     eval_const<M>(s, rec, z0, z1);
-                    fq_q(rec, z0, z1, q0, q1);
+                    q_of_record(rec, z0, z1, q0, q1);
                     if (bad) q0 = q1 = __builtin_nan("");
                     const double d0 = __dsub_rn(q0, s_c[jj]), d1 = __dsub_rn(q1, s_c[JT + jj]);
                     S[0][jj] = __dadd_rn(S[0][jj], d0);
@@ -165,19 +130,16 @@ __global__ __launch_bounds__(RM_THREADS) void k_fit_quality(const FqArgs a)
                     fq_row(Mn[1][jj], Sx[1][jj], q1);
                 }
             }
-            k += step_k;
-            w += step_w;
-            if (w >= Wp) { w -= Wp; ++k; }
+            at.next();
         }
-        // the 64 slots of a wave pairwise, then the four waves in ascending order
+        // the pairs merged in the order of the sums: within a wave, then the four waves
 #pragma unroll
         for (int v = 0; v < 2 * JT; ++v) {
             const int part = v / JT, jj = v % JT;
-            double xs = S[part][jj], xp = P[part][jj], m = Mn[part][jj], s = Sx[part][jj];
+            const double xs = wave_sum(S[part][jj]), xp = wave_sum(P[part][jj]);
+            double m = Mn[part][jj], s = Sx[part][jj];
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1) {
-                xs = __dadd_rn(xs, __shfl_xor(xs, d, 64));
-                xp = __dadd_rn(xp, __shfl_xor(xp, d, 64));
                 const double mb = __shfl_xor(m, d, 64), sb = __shfl_xor(s, d, 64);
                 fq_merge(m, s, mb, sb);
             }
@@ -193,8 +155,7 @@ __global__ __launch_bounds__(RM_THREADS) void k_fit_quality(const FqArgs a)
             const int part = tid / JT, jj = tid - part * JT, j = j0 + jj;
             if (j < N) {
                 const int vS = tid, vP = 2 * JT + tid, vM = 4 * JT + tid, vX = 6 * JT + tid;
-                const double Ss = __dadd_rn(__dadd_rn(__dadd_rn(s_wave[0][vS], s_wave[1][vS]), s_wave[2][vS]), s_wave[3][vS]);
-                const double Ps = __dadd_rn(__dadd_rn(__dadd_rn(s_wave[0][vP], s_wave[1][vP]), s_wave[2][vP]), s_wave[3][vP]);
+                const double Ss = waves_in_order(s_wave, vS), Ps = waves_in_order(s_wave, vP);
                 double m = s_wave[0][vM], s = s_wave[0][vX];
 #pragma unroll
                 for (int q = 1; q < 4; ++q) fq_merge(m, s, s_wave[q][vM], s_wave[q][vX]);
@@ -267,38 +228,21 @@ int bisip_fit_quality_dev(bisip_ctx *c, int64_t first_spectrum, int64_t n_spectr
 {
     int rc = check_response_shape(c, n_samples, n_spectra, walkers_per_ensemble);
     if (rc != BISIP_OK) return rc;
-    if (!d_chain) return fail(BISIP_EINVAL, "null argument");
-    if (!d_mean_q && !d_var_q && !d_lmeh) return fail(BISIP_EINVAL, "neither mean_q nor var_q nor lmeh asked for");
-    if (first_spectrum < 0 || first_spectrum + n_spectra > c->E)
-        return fail(BISIP_EINVAL, "spectra [%lld, %lld) of %d", (long long)first_spectrum, (long long)(first_spectrum + n_spectra), c->E);
-    if (sample_stride < n_spectra * walkers_per_ensemble * c->ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
-    if (((uintptr_t)d_chain % 8) || ((uintptr_t)d_mean_q % 8) || ((uintptr_t)d_var_q % 8) || ((uintptr_t)d_lmeh % 8) ||
-        ((uintptr_t)d_work % 8))
-        return fail(BISIP_EINVAL, "buffers must be 8-byte aligned");
-    const RmPlan p = rm_plan(n_samples, n_spectra, walkers_per_ensemble);
-    const long long need = fit_workspace(c, p, n_spectra);
-    if (need < 0)
-        return fail(BISIP_EUNSUPPORTED, "%lld segments of %lld spectra exceed one grid", p.nseg, (long long)n_spectra);
-    if (need && (!d_work || work_bytes < need))
-        return fail(BISIP_EINVAL, "workspace of %lld bytes, need %lld", (long long)(d_work ? work_bytes : 0), need);
-    HIP_TRY(hipSetDevice(c->device));
+    rc = check_row_buffers(c, first_spectrum, n_spectra, d_chain, sample_stride, walkers_per_ensemble,
+                           {d_mean_q, d_var_q, d_lmeh}, "mean_q nor var_q nor lmeh", d_work);
+    if (rc != BISIP_OK) return rc;
+    RmPlan p;
+    rc = plan_row_pass(c, n_samples, n_spectra, walkers_per_ensemble, fit_workspace, d_work, work_bytes, p);
+    if (rc != BISIP_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     FqArgs a{};
-    a.chain = d_chain; a.stride = sample_stride; a.R = p.R; a.seg_rows = p.seg_rows; a.nseg = p.nseg;
-    a.Wp = (int)walkers_per_ensemble; a.N = c->N;
-    a.cb = c->d_cb + first_spectrum * c->cb_stride; a.cb_stride = c->cb_stride;
+    fill_row_pass(a, c, first_spectrum, d_chain, sample_stride, walkers_per_ensemble, p);
     a.mean_q = d_mean_q; a.var_q = d_var_q; a.lmeh = d_lmeh;
     a.part = (double *)d_work;
     a.shift = (double *)d_work + n_spectra * p.nseg * 8 * c->N;
     rc = dispatch_fit(c, a, (unsigned)(n_spectra * p.nseg), st);
-    if (rc != BISIP_OK) return rc;
-    if (p.nseg > 1) {
-        hipLaunchKernelGGL(k_fit_merge, dim3((unsigned)n_spectra, (unsigned)((2 * c->N + RM_THREADS - 1) / RM_THREADS)),
-                           dim3(RM_THREADS), 0, st, a);
-        HIP_TRY(hipGetLastError());
-    }
-    return BISIP_OK;
+    if (rc != BISIP_OK || p.nseg == 1) return rc;
+    return launch_per_point(k_fit_merge, n_spectra, 2 * c->N, st, a);
 }
 
 }  // extern "C"

@@ -7,15 +7,13 @@
 // NumPy: the same bits of chi2_mean and the same counts from the same responses, and the same order of pit, p_chi2 and
 // p_max with glibc's functions in the place of the device library's.
 //
-// Rows, plan (rm_plan of response_plan.h; response.plan), row slots, segments: those of dispatch_fit.hip.  A workgroup of
-// 256 threads takes one (spectrum, segment); row i of a segment goes to slot i mod 256; a slot takes its rows in ascending
-// order and adds every term to a sum that starts from 0.0; the 256 slots are added pairwise within each wave of 64 slots,
-// 32, 16, ..., 1 apart; the four waves' results then in ascending order ((w0 + w1) + w2) + w3; segments in ascending order
-// by k_pred_finish, which divides by R.  Every term lies in [0, 1] or is >= 0: plain sums, no shift.  Nothing is fused.
+// Rows, plan, row slots, wave order, segments: row_pass.h.  A slot adds every term to a sum that starts from 0.0; the
+// segments are added by k_pred_finish, which divides by R.  Every term lies in [0, 1] or is >= 0: plain sums, no shift.
+// Nothing is fused.
 //
 // Two passes over the chain, each evaluating the model (M::setup / eval_const, the bits of forward()):
-//   * k_pred_rows, always: a row's frequencies in ascending order, one lane a row.  d = y - Z; t = d * d; q = t * iv (the
-//     bits of fitquality.pointwise_q); T = sum of q, Re before Im of each frequency, from 0.0; qmax = max q; C = pairs of
+//   * k_pred_rows, always: a row's frequencies in ascending order, one lane a row.  d and q: q_of_record (the bits of
+//     fitquality.pointwise_q); T = sum of q, Re before Im of each frequency, from 0.0; qmax = max q; C = pairs of
 //     adjacent frequencies, within Re and within Im, whose d < 0 differs.  A row with a parameter that is not finite or
 //     whose T is not finite is BAD: it is counted per (spectrum, segment), takes no histogram bin, and k_pred_finish
 //     makes every floating-point output of a spectrum with a bad row NaN.  A good row adds T, Q(N, T / 2) and
@@ -38,7 +36,7 @@
 //   k_pred_rows (exp, log, log1p, expm1, erfc and the two loops of Q inlined once): PolynomialDecomposition 147-163 up to
 //     degree 3 (three waves), 169-193 from degree 4 on (two); Cole-Cole 178-251 (two); Dias 175 (two); Shin 168 (three).
 //   k_pred_finish: 14 VGPRs.
-#include "response_plan.h"
+#include "row_pass.h"
 
 using namespace bisip;
 using namespace bisip::host;
@@ -48,12 +46,7 @@ namespace {
 constexpr int PC_JT = 8;                      // frequencies per tile of the point pass: 2 * PC_JT doubles of state per lane
 constexpr int PC_ROW_N_MAX = 700;             // above it exp(-x) underflows with x < N: the row outputs are refused
 
-struct PcArgs {
-    const double *chain;         // walker 0 of the call's first spectrum in the first used sample
-    long long stride, R, seg_rows, nseg;
-    int Wp, N;
-    const double *cb;            // records of the call's first spectrum
-    long long cb_stride;
+struct PcArgs : RowPass {
     double lgf;                  // log((N - 1)!)
     double *pit, *row;           // (n_spectra, 2, N), (n_spectra, 3); either may be null
     long long *hist;             // (n_spectra, 2N - 1); may be null
@@ -88,13 +81,6 @@ __device__ __forceinline__ double pc_max_sf(double n_points, double qmax)
     return -expm1(__dmul_rn(n_points, log1p(-e)));
 }
 
-__device__ __forceinline__ double pc_wave_sum(double x)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x = __dadd_rn(x, __shfl_xor(x, d, 64));
-    return x;
-}
-
 // grid (n_spectra * nseg), (2N - 1) ints of dynamic LDS when the histogram is asked for: workgroup b takes segment
 // b % nseg of spectrum b / nseg
 template <class M>
@@ -106,12 +92,10 @@ __global__ __launch_bounds__(RM_THREADS) void k_pred_rows(const PcArgs a)
     __shared__ int s_bad;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int N = a.N, Wp = a.Wp, bins = 2 * N - 1;
-    const long long e = blockIdx.x / a.nseg, g = blockIdx.x - e * a.nseg;
-    const long long r0 = g * a.seg_rows;
-    const int R = (int)(a.R - r0 < a.seg_rows ? a.R - r0 : a.seg_rows);
-    const double *__restrict__ base = a.chain + e * Wp * NDIM;
-    const double *__restrict__ cb = a.cb + e * a.cb_stride;
+    const int N = a.N, bins = 2 * N - 1;
+    RowCursor<NDIM> at(a, blockIdx.x, tid);
+    const long long e = at.e, g = at.g;
+    const double *__restrict__ cb = at.cb;
     const bool want_hist = a.hist != nullptr, want_row = a.row != nullptr;    // (uniform)
     const double n_points = (double)(2 * N);
 
@@ -120,35 +104,22 @@ __global__ __launch_bounds__(RM_THREADS) void k_pred_rows(const PcArgs a)
     if (tid == 0) s_bad = 0;
     __syncthreads();
 
-    const long long k0 = (r0 + tid) / Wp;
-    const int w0 = (int)(r0 + tid - k0 * Wp);
-    const int step_k = RM_THREADS / Wp, step_w = RM_THREADS - step_k * Wp;
-    long long k = k0;
-    int w = w0, n_bad = 0;
+    int n_bad = 0;
     double sT = 0.0, sQ = 0.0, sM = 0.0;
 #pragma unroll 1
-    for (int i = tid; i < R; i += RM_THREADS) {
-        const double *__restrict__ row = base + k * a.stride + (long long)w * NDIM;
+    for (int i = tid; i < at.R; i += RM_THREADS) {
         double th[NDIM];
-        bool bad = false;
-#pragma unroll
-        for (int q = 0; q < NDIM; ++q) {
-            th[q] = row[q];
-            bad |= !(fabs(th[q]) < HUGE_VAL);                       // NaN or +-inf
-        }
+        bool bad = load_row<NDIM>(at.row(), th);
         const typename M::Setup s = M::setup(th);
         double T = 0.0, qmax = 0.0;
         int C = 0;
         bool n0p = false, n1p = false;
 #pragma unroll 1
         for (int j = 0; j < N; ++j) {
-            typedef const double __attribute__((address_space(4))) *const_ptr;   // scalar loads, as eval_const
             const double *rec = cb + (long long)j * M::REC;
-            const const_ptr r = (const_ptr)rec;
-            double z0, z1;
+            double z0, z1, q0, q1, d0, d1;
             eval_const<M>(s, rec, z0, z1);
-            const double d0 = __dsub_rn(r[0], z0), d1 = __dsub_rn(r[1], z1);
-            const double q0 = __dmul_rn(__dmul_rn(d0, d0), r[2]), q1 = __dmul_rn(__dmul_rn(d1, d1), r[3]);
+            q_of_record(rec, z0, z1, q0, q1, d0, d1);
             T = __dadd_rn(__dadd_rn(T, q0), q1);
             qmax = fmax(qmax, fmax(q0, q1));
             const bool n0 = d0 < 0.0, n1 = d1 < 0.0;
@@ -171,14 +142,12 @@ __global__ __launch_bounds__(RM_THREADS) void k_pred_rows(const PcArgs a)
         sT = __dadd_rn(sT, T);
         sQ = __dadd_rn(sQ, Q);
         sM = __dadd_rn(sM, pm);
-        k += step_k;
-        w += step_w;
-        if (w >= Wp) { w -= Wp; ++k; }
+        at.next();
     }
     if (n_bad) atomicAdd(&s_bad, n_bad);
-    sT = pc_wave_sum(sT);
-    sQ = pc_wave_sum(sQ);
-    sM = pc_wave_sum(sM);
+    sT = wave_sum(sT);
+    sQ = wave_sum(sQ);
+    sM = wave_sum(sM);
     if (lane == 0) {
         s_wave[wave][0] = sT;
         s_wave[wave][1] = sQ;
@@ -186,7 +155,7 @@ __global__ __launch_bounds__(RM_THREADS) void k_pred_rows(const PcArgs a)
     }
     __syncthreads();
     double *__restrict__ p = a.part + (e * a.nseg + g) * (2 * N + 4) + 2 * N;
-    if (tid < 3) p[tid] = __dadd_rn(__dadd_rn(__dadd_rn(s_wave[0][tid], s_wave[1][tid]), s_wave[2][tid]), s_wave[3][tid]);
+    if (tid < 3) p[tid] = waves_in_order(s_wave, tid);
     if (tid == 3) ((long long *)p)[3] = (long long)s_bad;
     if (want_hist) {
         long long *__restrict__ h = a.hist + e * bins;
@@ -206,17 +175,10 @@ __global__ __launch_bounds__(RM_THREADS) void k_pred_points(const PcArgs a)
     __shared__ double s_wave[4][NV];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int N = a.N, Wp = a.Wp;
-    const long long e = blockIdx.x / a.nseg, g = blockIdx.x - e * a.nseg;
-    const long long r0 = g * a.seg_rows;
-    const int R = (int)(a.R - r0 < a.seg_rows ? a.R - r0 : a.seg_rows);
-    const double *__restrict__ base = a.chain + e * Wp * NDIM;
-    const double *__restrict__ cb = a.cb + e * a.cb_stride;
-    double *__restrict__ p = a.part + (e * a.nseg + g) * (2 * N + 4);
-
-    const long long k0 = (r0 + tid) / Wp;
-    const int w0 = (int)(r0 + tid - k0 * Wp);
-    const int step_k = RM_THREADS / Wp, step_w = RM_THREADS - step_k * Wp;
+    const int N = a.N;
+    RowCursor<NDIM> at(a, blockIdx.x, tid);
+    const double *__restrict__ cb = at.cb;
+    double *__restrict__ p = a.part + (at.e * a.nseg + at.g) * (2 * N + 4);
 
     for (int j0 = 0; j0 < N; j0 += JT) {
         if (tid < NV) {                                             // h of this tile's points
@@ -227,14 +189,11 @@ __global__ __launch_bounds__(RM_THREADS) void k_pred_points(const PcArgs a)
         double F[2][JT];
 #pragma unroll
         for (int jj = 0; jj < JT; ++jj) F[0][jj] = F[1][jj] = 0.0;
-        long long k = k0;
-        int w = w0;
+        at.rewind();
 #pragma unroll 1
-        for (int i = tid; i < R; i += RM_THREADS) {
-            const double *__restrict__ row = base + k * a.stride + (long long)w * NDIM;
+        for (int i = tid; i < at.R; i += RM_THREADS) {
             double th[NDIM];
-#pragma unroll
-            for (int q = 0; q < NDIM; ++q) th[q] = row[q];
+            load_row<NDIM>(at.row(), th);                           // (a row that is not finite is k_pred_rows' to count)
             const typename M::Setup s = M::setup(th);
 #pragma unroll
             for (int jj = 0; jj < JT; ++jj) {
@@ -250,20 +209,17 @@ __global__ __launch_bounds__(RM_THREADS) void k_pred_points(const PcArgs a)
                     F[1][jj] = __dadd_rn(F[1][jj], __dmul_rn(0.5, erfc(-a1)));
                 }
             }
-            k += step_k;
-            w += step_w;
-            if (w >= Wp) { w -= Wp; ++k; }
+            at.next();
         }
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
-            const double x = pc_wave_sum(F[v / JT][v % JT]);
+            const double x = wave_sum(F[v / JT][v % JT]);
             if (lane == 0) s_wave[wave][v] = x;
         }
         __syncthreads();
         if (tid < NV) {
             const int part = tid / JT, j = j0 + tid - part * JT;
-            if (j < N)
-                p[part * N + j] = __dadd_rn(__dadd_rn(__dadd_rn(s_wave[0][tid], s_wave[1][tid]), s_wave[2][tid]), s_wave[3][tid]);
+            if (j < N) p[part * N + j] = waves_in_order(s_wave, tid);
         }
         __syncthreads();                                            // s_h and s_wave are rewritten by the next tile
     }
@@ -340,41 +296,24 @@ int bisip_predictive_check_dev(bisip_ctx *c, int64_t first_spectrum, int64_t n_s
 {
     int rc = check_response_shape(c, n_samples, n_spectra, walkers_per_ensemble);
     if (rc != BISIP_OK) return rc;
-    if (!d_chain) return fail(BISIP_EINVAL, "null argument");
-    if (!d_pit && !d_row && !d_sign_changes) return fail(BISIP_EINVAL, "neither pit nor row nor sign_changes asked for");
-    if (first_spectrum < 0 || first_spectrum + n_spectra > c->E)
-        return fail(BISIP_EINVAL, "spectra [%lld, %lld) of %d", (long long)first_spectrum, (long long)(first_spectrum + n_spectra), c->E);
-    if (sample_stride < n_spectra * walkers_per_ensemble * c->ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
-    if (((uintptr_t)d_chain % 8) || ((uintptr_t)d_pit % 8) || ((uintptr_t)d_row % 8) || ((uintptr_t)d_sign_changes % 8) ||
-        ((uintptr_t)d_work % 8))
-        return fail(BISIP_EINVAL, "buffers must be 8-byte aligned");
+    rc = check_row_buffers(c, first_spectrum, n_spectra, d_chain, sample_stride, walkers_per_ensemble,
+                           {d_pit, d_row, d_sign_changes}, "pit nor row nor sign_changes", d_work);
+    if (rc != BISIP_OK) return rc;
     if ((d_row || d_sign_changes) && c->N > PC_ROW_N_MAX)
         return fail(BISIP_EUNSUPPORTED, "the row outputs of N=%d frequencies (at most %d)", c->N, PC_ROW_N_MAX);
-    const RmPlan p = rm_plan(n_samples, n_spectra, walkers_per_ensemble);
-    const long long need = predictive_workspace(c, p, n_spectra);
-    if (need < 0)
-        return fail(BISIP_EUNSUPPORTED, "%lld segments of %lld spectra exceed one grid", p.nseg, (long long)n_spectra);
-    if (!d_work || work_bytes < need)
-        return fail(BISIP_EINVAL, "workspace of %lld bytes, need %lld", (long long)(d_work ? work_bytes : 0), need);
-    HIP_TRY(hipSetDevice(c->device));
+    RmPlan p;
+    rc = plan_row_pass(c, n_samples, n_spectra, walkers_per_ensemble, predictive_workspace, d_work, work_bytes, p);
+    if (rc != BISIP_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     PcArgs a{};
-    a.chain = d_chain; a.stride = sample_stride; a.R = p.R; a.seg_rows = p.seg_rows; a.nseg = p.nseg;
-    a.Wp = (int)walkers_per_ensemble; a.N = c->N;
-    a.cb = c->d_cb + first_spectrum * c->cb_stride; a.cb_stride = c->cb_stride;
+    fill_row_pass(a, c, first_spectrum, d_chain, sample_stride, walkers_per_ensemble, p);
     a.lgf = log_factorial(c->N - 1);
     a.pit = d_pit; a.row = d_row; a.hist = d_sign_changes;
     a.part = (double *)d_work;
     if (d_sign_changes) HIP_TRY(hipMemsetAsync(d_sign_changes, 0, sizeof(long long) * (size_t)n_spectra * (2 * c->N - 1), st));
     rc = dispatch_predictive(c, a, (unsigned)(n_spectra * p.nseg), st);
-    if (rc != BISIP_OK) return rc;
-    if (d_pit || d_row) {
-        hipLaunchKernelGGL(k_pred_finish, dim3((unsigned)n_spectra, (unsigned)((2 * c->N + 3 + RM_THREADS - 1) / RM_THREADS)),
-                           dim3(RM_THREADS), 0, st, a);
-        HIP_TRY(hipGetLastError());
-    }
-    return BISIP_OK;
+    if (rc != BISIP_OK || !(d_pit || d_row)) return rc;
+    return launch_per_point(k_pred_finish, n_spectra, 2 * c->N + 3, st, a);
 }
 
 }  // extern "C"

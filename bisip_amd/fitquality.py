@@ -26,7 +26,7 @@ import warnings
 
 import numpy as np
 
-from .response import plan
+from .response import plan, row_pass_workspace
 
 __all__ = ('P_WAIC_HIGH', 'inverse_variance', 'pointwise_q', 'pointwise_log_lik', 'fit_sums', 'waic', 'waic_from_sums',
            'dic', 'compare_waic', 'ordered_fit_sums', 'device_fit_quality', 'ModelFitQuality', 'BatchFitQuality')
@@ -232,13 +232,7 @@ def device_fit_quality(view, ctx, first_spectrum=0):
     a ChainView: ``(n_ensembles, 2, N)`` each (NumPy), taken where the chain lies (bisip_fit_quality_dev).  Ensemble ``e``
     of the view is spectrum ``first_spectrum + e`` of the context."""
     import torch
-    n, E, Wp, ndim = view.n, view.n_ensembles, view.walkers_per_ensemble, view.ndim
-    if ndim != ctx.ndim:
-        raise ValueError(f'a chain of {ndim} parameters for a model of {ctx.ndim}')
-    nbytes = ctx.fit_quality_workspace(n, E, Wp)
-    if nbytes < 0:
-        raise ValueError(f'a chain of {E} ensembles of {Wp} walkers is too large for one launch')
-    work = view.empty((nbytes,), torch.uint8) if nbytes else None
+    n, E, Wp, work, nbytes = row_pass_workspace(view, ctx, ctx.fit_quality_workspace)
     out = view.empty((3, E, 2, ctx.N), torch.float64)
     ctx.fit_quality_dev(first_spectrum, E, view.ptr, n, view.stride, Wp, out[0].data_ptr(), out[1].data_ptr(),
                         out[2].data_ptr(), work.data_ptr() if nbytes else 0, nbytes, view.stream)
@@ -256,15 +250,9 @@ class ModelFitQuality:
         s = self._device_chain_sampler(chain, kwargs)
         if s is not None and s.n_ensembles == 1:      # fit(chain='device'): reduced where the chain lies
             return tuple(a[0] for a in s.fit_quality(**discard_thin(kwargs)))
-        import torch
-        from .chainview import ChainView
-        flat = np.ascontiguousarray(self.parse_chain(chain, **kwargs), dtype=np.float64)
-        ctx = self._context()
-        if flat.ndim != 2 or flat.shape[1] != ctx.ndim or flat.shape[0] < 1:
-            raise ValueError(f'the chain must be (n, {ctx.ndim}), n >= 1, got {flat.shape}')
-        # the chain goes up once; its rows are the rows of get_chain(flat=True): the same sums in the same order
-        t = torch.from_numpy(flat).to(torch.device('cuda', ctx.device))
-        return tuple(a[0] for a in device_fit_quality(ChainView(t, flat.shape[0], 1, 1, ctx.ndim), ctx))
+        from .chainview import host_chain_view
+        flat, ctx = self.parse_chain(chain, **kwargs), self._context()
+        return tuple(a[0] for a in device_fit_quality(host_chain_view(flat, ctx), ctx))
 
     def get_pointwise_misfit(self, chain=None, **kwargs):
         """The posterior mean of the squared standardised residual of every data point, ``(2, N)`` (Re, Im):

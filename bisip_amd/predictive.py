@@ -38,7 +38,7 @@ import warnings
 import numpy as np
 
 from .fitquality import inverse_variance, pointwise_q
-from .response import plan
+from .response import plan, row_pass_workspace
 
 __all__ = ('PIT_EXTREME', 'normal_cdf', 'chi2_sf_even', 'max_abs_sf', 'sign_changes', 'binomial_half_cdf',
            'predictive_sums', 'predictive_check', 'ordered_predictive_sums', 'device_predictive_check', 'ModelPredictive',
@@ -265,14 +265,8 @@ def device_predictive_check(view, ctx, first_spectrum=0):
     lies (bisip_predictive_check_dev); ``row`` holds chi2_mean, p_chi2 and p_max.  Ensemble ``e`` of the view is spectrum
     ``first_spectrum + e`` of the context."""
     import torch
-    n, E, Wp, ndim = view.n, view.n_ensembles, view.walkers_per_ensemble, view.ndim
-    if ndim != ctx.ndim:
-        raise ValueError(f'a chain of {ndim} parameters for a model of {ctx.ndim}')
-    nbytes = ctx.predictive_check_workspace(n, E, Wp)
-    if nbytes < 0:
-        raise ValueError(f'a chain of {E} ensembles of {Wp} walkers is too large for one launch')
+    n, E, Wp, work, nbytes = row_pass_workspace(view, ctx, ctx.predictive_check_workspace)      # (never 0 bytes)
     N = ctx.N
-    work = view.empty((nbytes,), torch.uint8)
     pit = view.empty((E, 2, N), torch.float64)
     row = view.empty((E, 3), torch.float64)
     hist = view.empty((E, 2 * N - 1), torch.int64)
@@ -291,15 +285,9 @@ class ModelPredictive:
         s = self._device_chain_sampler(chain, kwargs)
         if s is not None and s.n_ensembles == 1:      # fit(chain='device'): reduced where the chain lies
             return tuple(a[0] for a in s.predictive_check(**discard_thin(kwargs)))
-        import torch
-        from .chainview import ChainView
-        flat = np.ascontiguousarray(self.parse_chain(chain, **kwargs), dtype=np.float64)
-        ctx = self._context()
-        if flat.ndim != 2 or flat.shape[1] != ctx.ndim or flat.shape[0] < 1:
-            raise ValueError(f'the chain must be (n, {ctx.ndim}), n >= 1, got {flat.shape}')
-        # the chain goes up once; its rows are the rows of get_chain(flat=True): the same sums in the same order
-        t = torch.from_numpy(flat).to(torch.device('cuda', ctx.device))
-        return tuple(a[0] for a in device_predictive_check(ChainView(t, flat.shape[0], 1, 1, ctx.ndim), ctx))
+        from .chainview import host_chain_view
+        flat, ctx = self.parse_chain(chain, **kwargs), self._context()
+        return tuple(a[0] for a in device_predictive_check(host_chain_view(flat, ctx), ctx))
 
     def get_predictive_check(self, chain=None, **kwargs):
         """The posterior predictive checks of the fit (bisip_amd.predictive.predictive_check): a dict of ``pit (2, N)``,

@@ -72,7 +72,7 @@ def response_moments(Z, kind='ri'):
 
 
 # -- the device's order of summation ------------------------------------------------------------------------------------
-# dispatch_response.hip: RM_WGS, RM_ONE_SEGMENT, RM_SEG_MAX, RM_SEG_MIN, RM_THREADS
+# row_pass.h: RM_WGS, RM_ONE_SEGMENT, RM_SEG_MAX, RM_SEG_MIN, RM_THREADS
 WORKGROUPS_WANTED, ONE_SEGMENT_SPECTRA, SEGMENT_MAX, SEGMENT_MIN, SLOTS = 2048, 256, 1 << 30, 1024, 256
 
 
@@ -131,6 +131,20 @@ def ordered_response_moments(Z, kind='ri', n_spectra=None):
     return mean.reshape(E, 2, N), std.reshape(E, 2, N)
 
 
+def row_pass_workspace(view, ctx, workspace):
+    """``(n, E, Wp, work, nbytes)`` for one of the fused passes over the rows of a ChainView (bisip_response_moments_dev,
+    bisip_fit_quality_dev, bisip_predictive_check_dev): the view's shape, held against the model of ``ctx``, and the
+    ``nbytes`` of device scratch that ``workspace(n, E, Wp)`` of the context asks for (``work``: None for 0 bytes)."""
+    import torch
+    n, E, Wp = view.n, view.n_ensembles, view.walkers_per_ensemble
+    if view.ndim != ctx.ndim:
+        raise ValueError(f'a chain of {view.ndim} parameters for a model of {ctx.ndim}')
+    nbytes = workspace(n, E, Wp)
+    if nbytes < 0:
+        raise ValueError(f'a chain of {E} ensembles of {Wp} walkers is too large for one launch')
+    return n, E, Wp, (view.empty((nbytes,), torch.uint8) if nbytes else None), nbytes
+
+
 def device_model_moments(view, ctx, kind='ri', first_spectrum=0, mean=True, std=True):
     """``(mean, std)`` of the model response of ``ctx`` (a HipContext) over every ensemble's samples of a ChainView, in
     the representation ``kind``: ``(n_ensembles, 2, N)`` each (NumPy; None for the one not asked for), taken where the
@@ -138,15 +152,9 @@ def device_model_moments(view, ctx, kind='ri', first_spectrum=0, mean=True, std=
     context."""
     import torch
     _check_kind(kind)
-    n, E, Wp, ndim = view.n, view.n_ensembles, view.walkers_per_ensemble, view.ndim
-    if ndim != ctx.ndim:
-        raise ValueError(f'a chain of {ndim} parameters for a model of {ctx.ndim}')
-    if not (mean or std):
+    if view.ndim == ctx.ndim and not (mean or std):      # (a chain of another model is reported first, below)
         raise ValueError('neither mean nor std asked for')
-    nbytes = ctx.response_moments_workspace(n, E, Wp)
-    if nbytes < 0:
-        raise ValueError(f'a chain of {E} ensembles of {Wp} walkers is too large for one launch')
-    work = view.empty((nbytes,), torch.uint8) if nbytes else None
+    n, E, Wp, work, nbytes = row_pass_workspace(view, ctx, ctx.response_moments_workspace)
     m = view.empty((E, 2, ctx.N), torch.float64) if mean else None
     s = view.empty((E, 2, ctx.N), torch.float64) if std else None
     ctx.response_moments_dev(first_spectrum, E, view.ptr, n, view.stride, Wp, kind, m.data_ptr() if mean else 0,
@@ -182,15 +190,9 @@ class ModelResponse:
         if s is not None and s.n_ensembles == 1:      # fit(chain='device'): reduced where the chain lies
             mean, std = s.model_moments(kind, **discard_thin(kwargs))
             return mean[0], std[0]
-        import torch
-        from .chainview import ChainView
-        flat = np.ascontiguousarray(self.parse_chain(chain, **kwargs), dtype=np.float64)
-        ctx = self._context()
-        if flat.ndim != 2 or flat.shape[1] != ctx.ndim or flat.shape[0] < 1:
-            raise ValueError(f'the chain must be (n, {ctx.ndim}), n >= 1, got {flat.shape}')
-        # the chain goes up once; its rows are the rows of get_chain(flat=True): the same sums in the same order
-        t = torch.from_numpy(flat).to(torch.device('cuda', ctx.device))
-        mean, std = device_model_moments(ChainView(t, flat.shape[0], 1, 1, ctx.ndim), ctx, kind)
+        from .chainview import host_chain_view
+        flat, ctx = self.parse_chain(chain, **kwargs), self._context()
+        mean, std = device_model_moments(host_chain_view(flat, ctx), ctx, kind)
         return mean[0], std[0]
 
     def get_model_mean(self, chain=None, kind='ri', **kwargs):
