@@ -1,5 +1,6 @@
-// chain.h -- what the chain_*.hip units share: the error plumbing, the sum over a wave, the column toolkit and the one
-// segmented sort (both in chain_columns.hip), and the launch of a kernel that is a template of ndim.  A unit that
+// chain.h -- what the chain_*.hip units share: the error plumbing and the argument checks (chain_check.h), the sum over a
+// wave, the column toolkit and the one segmented sort (both in chain_columns.hip), and the launch of a kernel that is a
+// template of ndim.  A unit that
 // summarises a device-resident chain includes this header and nothing of the samplers' (host.h, kernels.h); the two
 // units that take lag sums include it through chain_lags.h.
 #pragma once
@@ -11,7 +12,7 @@
 #include <vector>
 
 #include "../../include/bisip_hip.h"
-#include "errors.h"
+#include "chain_check.h"
 
 namespace bisip {
 
@@ -35,7 +36,6 @@ int gather_columns_by_sample(const double *d_chain, long long n_samples, long lo
                              int ndim, double *cols, hipStream_t st);
 
 // the segmented radix sort of `segments` contiguous segments of n doubles each (items = segments * n < 2^31)
-size_t align256(size_t x);
 int sort_temp_bytes(long long items, long long segments, long long n, size_t *bytes);
 size_t sort_scratch_bound(long long items, long long segments);
 int sort_segments(void *d_temp, size_t temp, const double *in, double *out, long long items, long long segments, long long n,
@@ -61,7 +61,7 @@ int launch_by_ndim(int ndim, dim3 grid, hipStream_t st, const Args &args)
     case 14: Launch<14>::run(grid, st, args); break;
     case 15: Launch<15>::run(grid, st, args); break;
     case 16: Launch<16>::run(grid, st, args); break;
-    default: return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
+    default: return fail(BISIP_EINVAL, "no kernel of ndim=%d", ndim);       // (the entry points check ndim first)
     }
     HIP_TRY(hipGetLastError());
     return BISIP_OK;

@@ -236,13 +236,13 @@ Layout layout(long long n_t, long long E, long long Wp, int ndim)
     return l;
 }
 
-bool shape_ok(int64_t n_samples, int64_t E, int64_t Wp, int ndim)
+// ndim, then the counts.  E: one window workgroup per (e, d); Wp: the tiles within one grid dimension and the walker
+// groups within grid dimension y.  n is not capped.
+int check_shape(const ChainShape &s, Voice v)
 {
-    if (n_samples < 1 || E < 1 || Wp < 1 || ndim < 1 || ndim > BISIP_MAX_NDIM) return false;
-    if (E > 0x7fffffffLL / ndim) return false;                        // one window workgroup per (e, d)
-    if (Wp > (0x7fffffffLL * LAG_TILE) / (E * ndim)) return false;    // tiles within one grid dimension
-    if (Wp > 65535LL * LAG_GROUP) return false;                       // walker groups within grid dimension y
-    return true;
+    BISIP_TRY(check_ndim(s.ndim, 1, v));
+    BISIP_TRY(check_counts(s, NO_CAP, GRID_MAX / s.ndim, NO_CAP, v));
+    return check_counts(s, NO_CAP, NO_CAP, std::min<int64_t>(GRID_MAX * LAG_TILE / (s.E * s.ndim), 65535LL * LAG_GROUP), v);
 }
 
 }  // namespace
@@ -251,7 +251,7 @@ extern "C" {
 
 int64_t bisip_chain_autocorr_time_workspace(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim)
 {
-    if (!shape_ok(n_samples, n_ensembles, walkers_per_ensemble, ndim)) return 0;
+    if (check_shape({n_samples, 0, n_ensembles, walkers_per_ensemble, ndim}, QUIET) != BISIP_OK) return 0;
     return (int64_t)layout(n_samples, n_ensembles, walkers_per_ensemble, ndim).total;
 }
 
@@ -260,10 +260,9 @@ int bisip_chain_autocorr_time_dev(const double *d_chain, int64_t n_samples, int6
                                   void *d_work, void *stream)
 {
     if (!d_chain || !d_tau || !d_work) return fail(BISIP_EINVAL, "null argument");
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
-    if (!shape_ok(n_samples, n_ensembles, walkers_per_ensemble, ndim)) return fail(BISIP_EINVAL, "bad chain shape");
-    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
+    const ChainShape s{n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim};
+    BISIP_TRY(check_shape(s, LOUD));
+    BISIP_TRY(check_stride(s));
     if (!(c > 0.0) || !std::isfinite(c)) return fail(BISIP_EINVAL, "c=%g: the window factor must be finite and > 0", c);
     const Layout l = layout(n_samples, n_ensembles, walkers_per_ensemble, ndim);
     char *base = (char *)d_work;

@@ -315,18 +315,8 @@ __global__ __launch_bounds__(BR_THREADS) void k_bridge_iterate(const IterArgs a)
 }
 
 // -- host ------------------------------------------------------------------------------------------------------------------
-int check_ndim(int ndim)
-{
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
-    return BISIP_OK;
-}
-
-// blocks of 256 for n values of each of E ensembles: blocks per ensemble, or -1 when they exceed one grid
-long long blocks_per_ensemble(long long E, long long n)
-{
-    const long long bpe = (n + BR_THREADS - 1) / BR_THREADS;
-    return bpe > 0x7fffffffLL / E ? -1 : bpe;
-}
+// blocks of 256 for n values of one ensemble
+long long blocks_per_ensemble(long long n) { return (n + BR_THREADS - 1) / BR_THREADS; }
 
 template <int NDIM>
 struct LaunchLogg {
@@ -364,18 +354,13 @@ int bisip_bridge_logg_dev(const double *d_chain, int64_t n_samples, int64_t samp
                           const double *d_mean, const double *d_chol, const double *d_const, double *d_l, void *stream)
 {
     if (!d_chain || !d_logp || !d_mean || !d_chol || !d_const || !d_l) return fail(BISIP_EINVAL, "null argument");
-    int rc = check_ndim(ndim);
-    if (rc != BISIP_OK) return rc;
-    if (n_samples < 1 || n_samples > 0x7fffffffLL || n_ensembles < 1 || n_ensembles > 0x7fffffffLL ||
-        walkers_per_ensemble < 1 || walkers_per_ensemble > 0x7fffffffLL / (2 * BISIP_MAX_NDIM))
-        return fail(BISIP_EINVAL, "bad chain shape");
-    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
+    // the caps of bisip_chain_cov_dev: the kernel walks the rows of a segment as the covariance does
+    BISIP_TRY(check_chain({n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim}, 1, GRID_MAX, GRID_MAX,
+                          GRID_MAX / (2 * BISIP_MAX_NDIM)));
     if (logp_stride < n_ensembles * walkers_per_ensemble) return fail(BISIP_EINVAL, "logp_stride smaller than one sample");
     const long long N = n_samples * walkers_per_ensemble;
     const Segments p = logg_segments(N, n_ensembles);
-    if (p.nseg > 0x7fffffffLL / n_ensembles)
-        return fail(BISIP_EUNSUPPORTED, "%lld segments of %lld ensembles exceed one grid", p.nseg, (long long)n_ensembles);
+    BISIP_TRY(check_segment_grid(p.nseg, n_ensembles));
     LoggArgs a{};
     a.chain = d_chain; a.logp = d_logp; a.mean = d_mean; a.chol = d_chol; a.cst = d_const;
     a.cstride = sample_stride; a.lstride = logp_stride; a.N = N; a.seg_rows = p.seg_rows; a.nseg = p.nseg;
@@ -388,16 +373,14 @@ int bisip_bridge_draw_dev(const double *d_mean, const double *d_chol, const doub
                           double *d_logg, void *stream)
 {
     if (!d_mean || !d_chol || !d_const || !d_theta || !d_logg) return fail(BISIP_EINVAL, "null argument");
-    int rc = check_ndim(ndim);
-    if (rc != BISIP_OK) return rc;
+    BISIP_TRY(check_ndim(ndim));
     if (n_ensembles < 1 || n_ensembles > 0x7fffffffLL || n_draws < 1 || n_draws > (1LL << 40))
         return fail(BISIP_EINVAL, "bad shape: %lld draws of %lld ensembles", (long long)n_draws, (long long)n_ensembles);
     if (first_ensemble < 0 || first_ensemble + n_ensembles > 0x100000000LL)
         return fail(BISIP_EINVAL, "ensembles %lld ... do not fit the 32-bit counter word", (long long)first_ensemble);
     if (first_draw > UINT64_MAX - (uint64_t)n_draws) return fail(BISIP_EINVAL, "first_draw + n_draws exceeds 64 bits");
-    const long long bpe = blocks_per_ensemble(n_ensembles, n_draws);
-    if (bpe < 0) return fail(BISIP_EUNSUPPORTED, "%lld draws of %lld ensembles exceed one grid", (long long)n_draws,
-                             (long long)n_ensembles);
+    const long long bpe = blocks_per_ensemble(n_draws);
+    BISIP_TRY(check_grid(bpe, n_ensembles, LOUD, "%lld draws of %lld ensembles", (long long)n_draws, (long long)n_ensembles));
     DrawArgs a{};
     a.mean = d_mean; a.chol = d_chol; a.cst = d_const; a.n_draws = n_draws; a.bpe = bpe; a.seed = seed;
     a.first_draw = first_draw; a.first_ensemble = (unsigned long long)first_ensemble; a.theta = d_theta; a.logg = d_logg;
@@ -411,9 +394,9 @@ int bisip_bridge_scale_dev(const double *d_l1, int64_t n1, const double *d_logp2
     if (n_ensembles < 1 || n_ensembles > 0x7fffffffLL || n1 < 1 || n2 < 1 || n1 > (1LL << 40) || n2 > (1LL << 40))
         return fail(BISIP_EINVAL, "bad shape: %lld and %lld values of %lld ensembles", (long long)n1, (long long)n2,
                     (long long)n_ensembles);
-    const long long b1 = blocks_per_ensemble(n_ensembles, n1), b2 = blocks_per_ensemble(n_ensembles, n2);
-    if (b1 < 0 || b2 < 0) return fail(BISIP_EUNSUPPORTED, "%lld values of %lld ensembles exceed one grid",
-                                      (long long)(n1 > n2 ? n1 : n2), (long long)n_ensembles);
+    const long long b1 = blocks_per_ensemble(n1), b2 = blocks_per_ensemble(n2);
+    BISIP_TRY(check_grid(b1 > b2 ? b1 : b2, n_ensembles, LOUD, "%lld values of %lld ensembles", (long long)(n1 > n2 ? n1 : n2),
+                         (long long)n_ensembles));
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_bridge_scale, dim3((unsigned)(n_ensembles * b2)), dim3(BR_THREADS), 0, st, d_lstar, d_logp2, d_logg2,
                        (long long)n2, b2, 1, d_l2, d_a1);

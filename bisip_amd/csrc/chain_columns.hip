@@ -456,7 +456,7 @@ int gather_columns_by_sample(const double *d_chain, long long n_samples, long lo
                              int ndim, double *cols, hipStream_t st)
 {
     const long long tiles = n_samples * E * ((Wp + 63) / 64) * ((ndim + 63) / 64);
-    if (tiles > 0x7fffffffLL) return fail(BISIP_EUNSUPPORTED, "%lld tiles exceed one grid", tiles);
+    BISIP_TRY(check_grid(tiles, 1, LOUD, "%lld tiles", tiles));
     const GatherArgs g{d_chain, n_samples, sample_stride, E, Wp, ndim, cols, 1};
     hipLaunchKernelGGL(k_gather_columns_tiled, dim3((unsigned)tiles), dim3(256), 0, st, g);
     HIP_TRY(hipGetLastError());
@@ -484,8 +484,7 @@ static int percentiles_impl(const double *d_chain, int64_t n_samples, int64_t sa
     if (!d_chain || !percentiles || !d_out || !d_work) return fail(BISIP_EINVAL, "null argument");
     if (n_samples < 1 || n_ensembles < 1 || walkers_per_ensemble < 1 || n_percentiles < 1 || n_percentiles > 1024)
         return fail(BISIP_EINVAL, "bad shape");
-    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
+    BISIP_TRY(check_stride({n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim}));
     const long long n = n_samples * walkers_per_ensemble, columns = n_ensembles * ndim, items = n * columns;
     if (items > 0x7fffffffLL) return fail(BISIP_EUNSUPPORTED, "chain of %lld values exceeds the 2^31 items of one sort", items);
     for (int k = 0; k < n_percentiles; ++k)
@@ -494,8 +493,7 @@ static int percentiles_impl(const double *d_chain, int64_t n_samples, int64_t sa
     int rc = sort_temp_bytes(items, columns, n, &temp);
     if (rc != BISIP_OK) return rc;
     const size_t col_bytes = align256((size_t)items * 8);
-    const size_t need = 2 * col_bytes + align256(temp) + align256((size_t)n_percentiles * 16);
-    if (work_bytes < (int64_t)need) return fail(BISIP_EINVAL, "workspace of %lld bytes, need %zu", (long long)work_bytes, need);
+    BISIP_TRY(check_workspace(d_work, work_bytes, (int64_t)(2 * col_bytes + align256(temp) + align256((size_t)n_percentiles * 16))));
     char *base = (char *)d_work;
     double *cols = (double *)base, *sorted = (double *)(base + col_bytes);
     void *d_temp = base + 2 * col_bytes;
@@ -588,7 +586,7 @@ int bisip_chain_percentiles_dev(const double *d_chain, int64_t n_samples, int64_
                                 const double *percentiles, int n_percentiles, double *d_out,
                                 void *d_work, int64_t work_bytes, void *stream)
 {
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
+    BISIP_TRY(check_ndim(ndim));
     return percentiles_impl(d_chain, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, percentiles,
                             n_percentiles, d_out, d_work, work_bytes, stream);
 }

@@ -277,22 +277,18 @@ void cv_launch(const CovArgs &a, unsigned blocks, hipStream_t st)
     hipLaunchKernelGGL(k_cov_accumulate<NDIM>, dim3(blocks), dim3(CV_THREADS), 0, st, a);
 }
 
-int check_rows_shape(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble)
+// n, E: 32 bits; Wp: the kernel's element numbers within a sample reach 2 * Wp * ndim and are ints (w in its load)
+int check_rows_shape(const ChainShape &s, Voice v)
 {
-    if (n_samples < 1 || n_samples > 0x7fffffffLL || n_ensembles < 1 || n_ensembles > 0x7fffffffLL ||
-        walkers_per_ensemble < 1 || walkers_per_ensemble > 0x7fffffffLL / (2 * BISIP_MAX_NDIM))
-        return fail(BISIP_EINVAL, "bad chain shape");
-    return BISIP_OK;
+    return check_counts(s, GRID_MAX, GRID_MAX, GRID_MAX / (2 * BISIP_MAX_NDIM), v);
 }
 
-int check_cov_shape(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim)
+int check_cov_shape(const ChainShape &s, Voice v)
 {
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
-    int rc = check_rows_shape(n_samples, n_ensembles, walkers_per_ensemble);
-    if (rc != BISIP_OK) return rc;
-    if (n_samples * walkers_per_ensemble < 2)
-        return fail(BISIP_EINVAL, "a covariance needs 2 rows, got n_samples * walkers_per_ensemble = %lld",
-                    (long long)(n_samples * walkers_per_ensemble));
+    BISIP_TRY(check_ndim(s.ndim, 1, v));
+    BISIP_TRY(check_rows_shape(s, v));
+    if (s.n * s.Wp < 2)
+        return refuse(v, BISIP_EINVAL, "a covariance needs 2 rows, got n_samples * walkers_per_ensemble = %lld", (long long)(s.n * s.Wp));
     return BISIP_OK;
 }
 
@@ -390,9 +386,9 @@ extern "C" {
 
 int64_t bisip_chain_cov_workspace(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim)
 {
-    if (check_cov_shape(n_samples, n_ensembles, walkers_per_ensemble, ndim) != BISIP_OK) return -1;
+    if (check_cov_shape({n_samples, 0, n_ensembles, walkers_per_ensemble, ndim}, QUIET) != BISIP_OK) return -1;
     const RowPlan p = cv_plan(n_samples, n_ensembles, walkers_per_ensemble);
-    if (p.nseg > 0x7fffffffLL / n_ensembles) return -1;
+    if (check_segment_grid(p.nseg, n_ensembles, QUIET) != BISIP_OK) return -1;
     return p.nseg > 1 ? 8 * n_ensembles * p.nseg * cv_sums(ndim) : 0;
 }
 
@@ -401,16 +397,12 @@ int bisip_chain_cov_dev(const double *d_chain, int64_t n_samples, int64_t sample
                         int64_t work_bytes, void *stream)
 {
     if (!d_chain || !d_cov) return fail(BISIP_EINVAL, "null argument");
-    int rc = check_cov_shape(n_samples, n_ensembles, walkers_per_ensemble, ndim);
-    if (rc != BISIP_OK) return rc;
-    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
+    const ChainShape s{n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim};
+    BISIP_TRY(check_cov_shape(s, LOUD));
+    BISIP_TRY(check_stride(s));
     const RowPlan p = cv_plan(n_samples, n_ensembles, walkers_per_ensemble);
-    if (p.nseg > 0x7fffffffLL / n_ensembles)
-        return fail(BISIP_EUNSUPPORTED, "%lld segments of %lld ensembles exceed one grid", p.nseg, (long long)n_ensembles);
-    const long long need = p.nseg > 1 ? 8 * n_ensembles * p.nseg * cv_sums(ndim) : 0;
-    if (need && (!d_work || work_bytes < need))
-        return fail(BISIP_EINVAL, "workspace of %lld bytes, need %lld", (long long)(d_work ? work_bytes : 0), need);
+    BISIP_TRY(check_segment_grid(p.nseg, n_ensembles));
+    BISIP_TRY(check_workspace(d_work, work_bytes, p.nseg > 1 ? 8 * n_ensembles * p.nseg * cv_sums(ndim) : 0));
     hipStream_t st = (hipStream_t)stream;
     CovArgs a{};
     a.chain = d_chain; a.stride = sample_stride; a.N = p.N; a.seg_rows = p.seg_rows; a.nseg = p.nseg;
@@ -444,9 +436,9 @@ int bisip_chain_cov_dev(const double *d_chain, int64_t n_samples, int64_t sample
 
 int64_t bisip_chain_best_sample_workspace(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble)
 {
-    if (check_rows_shape(n_samples, n_ensembles, walkers_per_ensemble) != BISIP_OK) return -1;
+    if (check_rows_shape({n_samples, 0, n_ensembles, walkers_per_ensemble, 1}, QUIET) != BISIP_OK) return -1;
     const RowPlan p = bs_plan(n_samples, n_ensembles, walkers_per_ensemble);
-    if (p.nseg > 0x7fffffffLL / n_ensembles) return -1;
+    if (check_segment_grid(p.nseg, n_ensembles, QUIET) != BISIP_OK) return -1;
     return p.nseg > 1 ? 16 * n_ensembles * p.nseg : 0;
 }
 
@@ -458,19 +450,16 @@ int bisip_chain_best_sample_dev(const double *d_chain, int64_t chain_stride, con
     if (!d_logp) return fail(BISIP_EINVAL, "null argument");
     if (!d_theta && !d_best_logp && !d_index) return fail(BISIP_EINVAL, "none of theta, log-probability and index asked for");
     if (d_theta && !d_chain) return fail(BISIP_EINVAL, "theta asked for without a chain");
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
-    int rc = check_rows_shape(n_samples, n_ensembles, walkers_per_ensemble);
-    if (rc != BISIP_OK) return rc;
+    BISIP_TRY(check_ndim(ndim));
+    BISIP_TRY(check_rows_shape({n_samples, chain_stride, n_ensembles, walkers_per_ensemble, ndim}, LOUD));
+    // (two strides with names of their own; the caps on E and Wp keep both products within 64 bits)
     if (logp_stride < n_ensembles * walkers_per_ensemble)
         return fail(BISIP_EINVAL, "logp_stride smaller than one sample");
     if (d_chain && chain_stride < n_ensembles * walkers_per_ensemble * ndim)
         return fail(BISIP_EINVAL, "chain_stride smaller than one sample");
     const RowPlan p = bs_plan(n_samples, n_ensembles, walkers_per_ensemble);
-    if (p.nseg > 0x7fffffffLL / n_ensembles)
-        return fail(BISIP_EUNSUPPORTED, "%lld segments of %lld ensembles exceed one grid", p.nseg, (long long)n_ensembles);
-    const long long need = p.nseg > 1 ? 16 * n_ensembles * p.nseg : 0;
-    if (need && (!d_work || work_bytes < need))
-        return fail(BISIP_EINVAL, "workspace of %lld bytes, need %lld", (long long)(d_work ? work_bytes : 0), need);
+    BISIP_TRY(check_segment_grid(p.nseg, n_ensembles));
+    BISIP_TRY(check_workspace(d_work, work_bytes, p.nseg > 1 ? 16 * n_ensembles * p.nseg : 0));
     hipStream_t st = (hipStream_t)stream;
     BestArgs a{};
     a.chain = d_chain; a.logp = d_logp; a.cstride = chain_stride; a.lstride = logp_stride; a.N = p.N;

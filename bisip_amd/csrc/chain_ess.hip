@@ -318,15 +318,16 @@ struct Layout {
     size_t mean, cmin, cmax, R, part, state, t, done, total;
 };
 
-bool ess_shape_ok(int64_t n, int64_t E, int64_t Wp, int ndim, int splits, int n_threshold)
+// ndim, the splits, the samples of a half, then the counts.  n: 32 bits; E: one scan workgroup per (threshold, ensemble,
+// parameter) of ESS_MAX_THRESHOLDS thresholds; Wp: the tiles within grid dimension x and the chain groups of both halves
+// within grid dimension y.  (The number of thresholds is the entry point's to check.)
+int check_ess_shape(const ChainShape &s, int splits, Voice v)
 {
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM || (splits != 1 && splits != 2)) return false;
-    if (n_threshold < 0 || n_threshold > ESS_MAX_THRESHOLDS) return false;
-    if (n < 2 * splits || E < 1 || Wp < 1) return false;
-    if (n > 0x7fffffffLL || E > 0x7fffffffLL / (ndim * ESS_MAX_THRESHOLDS)) return false;   // one scan workgroup per pair
-    if (Wp > (0x7fffffffLL * LAG_TILE) / (E * ndim)) return false;                          // tiles within grid dimension x
-    if (2 * Wp > 65535LL * LAG_GROUP) return false;                                         // chain groups within dimension y
-    return true;
+    BISIP_TRY(check_ndim(s.ndim, 1, v));
+    if (splits != 1 && splits != 2) return refuse(v, BISIP_EINVAL, "splits=%d: 1 or 2", splits);
+    if (s.n < 2 * splits) return refuse(v, BISIP_EINVAL, "n_samples=%lld: a chain needs 2 samples, a half too", (long long)s.n);
+    BISIP_TRY(check_counts(s, GRID_MAX, GRID_MAX / (s.ndim * ESS_MAX_THRESHOLDS), NO_CAP, v));
+    return check_counts(s, NO_CAP, NO_CAP, std::min<int64_t>(GRID_MAX * LAG_TILE / (s.E * s.ndim), 65535LL * LAG_GROUP / 2), v);
 }
 
 Layout ess_layout(long long n, long long E, long long Wp, int ndim, int splits, int n_threshold)
@@ -360,17 +361,11 @@ int ess_run(const double *d_chain, int64_t n_samples, int64_t sample_stride, int
             int64_t walkers_per_ensemble, int ndim, int splits, int mode, const double *d_aux, int n_threshold,
             double *d_ess, void *d_work, int64_t work_bytes, void *stream)
 {
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
-    if (splits != 1 && splits != 2) return fail(BISIP_EINVAL, "splits=%d: 1 or 2", splits);
-    if (n_samples < 2 * splits)
-        return fail(BISIP_EINVAL, "n_samples=%lld: a chain needs 2 samples, a half too", (long long)n_samples);
-    if (!ess_shape_ok(n_samples, n_ensembles, walkers_per_ensemble, ndim, splits, n_threshold))
-        return fail(BISIP_EINVAL, "bad chain shape");
-    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
+    const ChainShape s{n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim};
+    BISIP_TRY(check_ess_shape(s, splits, LOUD));
+    BISIP_TRY(check_stride(s));
     const Layout l = ess_layout(n_samples, n_ensembles, walkers_per_ensemble, ndim, splits, n_threshold);
-    if (work_bytes < (int64_t)l.total)
-        return fail(BISIP_EINVAL, "workspace of %lld bytes, need %zu", (long long)work_bytes, l.total);
+    BISIP_TRY(check_workspace(d_work, work_bytes, (int64_t)l.total));
     char *base = (char *)d_work;
     EssArgs a{};
     a.chain = d_chain; a.n = n_samples; a.stride = sample_stride; a.E = n_ensembles; a.Wp = walkers_per_ensemble;
@@ -503,18 +498,19 @@ struct RankPlan {
     size_t col_bytes, temp_bytes, need;
 };
 
-bool rank_plan(int64_t n, int64_t E, int64_t Wp, int ndim, RankPlan &p)
+// ndim and the counts, none of which is capped as a bad shape: a chain beyond the 2^31 items of one sort is unsupported
+int rank_plan(int64_t n, int64_t E, int64_t Wp, int ndim, RankPlan &p, Voice v)
 {
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM || n < 1 || E < 1 || Wp < 1) return false;
-    if (n > 0x7fffffffLL || E > 0x7fffffffLL || Wp > 0x7fffffffLL) return false;
-    p.N = n * Wp;
-    p.columns = E * ndim;
-    if (p.N > 0x7fffffffLL || p.columns > 0x7fffffffLL || p.N * p.columns > 0x7fffffffLL) return false;
+    BISIP_TRY(check_ndim(ndim, 1, v));
+    BISIP_TRY(check_counts({n, 0, E, Wp, ndim}, NO_CAP, NO_CAP, NO_CAP, v));
+    if (n > GRID_MAX || E > GRID_MAX || Wp > GRID_MAX || (p.N = n * Wp) > GRID_MAX || (p.columns = E * ndim) > GRID_MAX ||
+        p.N * p.columns > GRID_MAX)
+        return refuse(v, BISIP_EUNSUPPORTED, "chain exceeds the 2^31 items of one sort");
     p.items = p.N * p.columns;
     p.col_bytes = align256((size_t)p.items * 8);
     p.temp_bytes = sort_scratch_bound(p.items, p.columns);
     p.need = 2 * p.col_bytes + align256(p.temp_bytes);
-    return true;
+    return BISIP_OK;
 }
 
 // what bisip_chain_rank_normalize_dev (d_center null) and bisip_chain_rank_normalize_folded_dev share
@@ -522,15 +518,10 @@ int rank_run(const double *d_chain, int64_t n_samples, int64_t sample_stride, in
              int64_t walkers_per_ensemble, int ndim, const double *d_center, double *d_z, void *d_work, int64_t work_bytes,
              void *stream)
 {
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
-    if (n_samples < 1 || n_ensembles < 1 || walkers_per_ensemble < 1) return fail(BISIP_EINVAL, "bad chain shape");
     RankPlan p{};
-    if (!rank_plan(n_samples, n_ensembles, walkers_per_ensemble, ndim, p))
-        return fail(BISIP_EUNSUPPORTED, "chain exceeds the 2^31 items of one sort");
-    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
-    if (work_bytes < (int64_t)p.need)
-        return fail(BISIP_EINVAL, "workspace of %lld bytes, need %zu", (long long)work_bytes, p.need);
+    BISIP_TRY(rank_plan(n_samples, n_ensembles, walkers_per_ensemble, ndim, p, LOUD));
+    BISIP_TRY(check_stride({n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim}));
+    BISIP_TRY(check_workspace(d_work, work_bytes, (int64_t)p.need));
     hipStream_t st = (hipStream_t)stream;
     char *base = (char *)d_work;
     double *cols = (double *)base, *sorted = (double *)(base + p.col_bytes);
@@ -555,7 +546,8 @@ extern "C" {
 int64_t bisip_chain_ess_workspace(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim, int splits,
                                   int n_threshold)
 {
-    if (!ess_shape_ok(n_samples, n_ensembles, walkers_per_ensemble, ndim, splits, n_threshold)) return 0;
+    if (n_threshold < 0 || n_threshold > ESS_MAX_THRESHOLDS) return 0;
+    if (check_ess_shape({n_samples, 0, n_ensembles, walkers_per_ensemble, ndim}, splits, QUIET) != BISIP_OK) return 0;
     return (int64_t)ess_layout(n_samples, n_ensembles, walkers_per_ensemble, ndim, splits, n_threshold).total;
 }
 
@@ -582,7 +574,7 @@ int bisip_chain_ess_squares_dev(const double *d_chain, int64_t n_samples, int64_
 int64_t bisip_chain_rank_normalize_workspace(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim)
 {
     RankPlan p{};
-    if (!rank_plan(n_samples, n_ensembles, walkers_per_ensemble, ndim, p)) return 0;
+    if (rank_plan(n_samples, n_ensembles, walkers_per_ensemble, ndim, p, QUIET) != BISIP_OK) return 0;
     return (int64_t)p.need;
 }
 

@@ -186,27 +186,25 @@ int hdi_path(long long n, long long columns, long long m_max)
     return path;
 }
 
-// checks everything but pointers and the workspace; quiet: the workspace function only reports < 0
+// checks everything but pointers, the stride and the workspace; QUIET: the workspace function only reports < 0.  No
+// count is capped as a bad shape: a chain beyond the 2^31 items of one sort is unsupported, after the windows are counted.
 int make_plan(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim, int n_windows,
-              const int64_t *windows, HdiPlan &p, bool quiet)
+              const int64_t *windows, HdiPlan &p, Voice v)
 {
-#define HDI_REFUSE(code, ...) return quiet ? (code) : fail((code), __VA_ARGS__)
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM) HDI_REFUSE(BISIP_EINVAL, "ndim=%d out of range", ndim);
-    if (n_samples < 1 || n_ensembles < 1 || walkers_per_ensemble < 1) HDI_REFUSE(BISIP_EINVAL, "bad chain shape");
+    BISIP_TRY(check_ndim(ndim, 1, v));
+    BISIP_TRY(check_counts({n_samples, 0, n_ensembles, walkers_per_ensemble, ndim}, NO_CAP, NO_CAP, NO_CAP, v));
     if (n_windows < 1 || n_windows > HDI_MAX_WINDOWS)
-        HDI_REFUSE(BISIP_EINVAL, "n_windows=%d out of range (1 ... %d)", n_windows, HDI_MAX_WINDOWS);
-    if (!windows) HDI_REFUSE(BISIP_EINVAL, "null argument");
-    if (n_samples > 0x7fffffffLL || n_ensembles > 0x7fffffffLL || walkers_per_ensemble > 0x7fffffffLL)
-        HDI_REFUSE(BISIP_EUNSUPPORTED, "chain exceeds the 2^31 items of one sort");
-    p.n = n_samples * walkers_per_ensemble;
-    p.columns = n_ensembles * ndim;
-    if (p.n > 0x7fffffffLL || p.columns > 0x7fffffffLL || p.n * p.columns > 0x7fffffffLL)
-        HDI_REFUSE(BISIP_EUNSUPPORTED, "chain exceeds the 2^31 items of one sort");
+        return refuse(v, BISIP_EINVAL, "n_windows=%d out of range (1 ... %d)", n_windows, HDI_MAX_WINDOWS);
+    if (!windows) return refuse(v, BISIP_EINVAL, "null argument");
+    if (n_samples > GRID_MAX || n_ensembles > GRID_MAX || walkers_per_ensemble > GRID_MAX ||     // (then the products fit)
+        (p.n = n_samples * walkers_per_ensemble) > GRID_MAX || (p.columns = n_ensembles * ndim) > GRID_MAX ||
+        p.n * p.columns > GRID_MAX)
+        return refuse(v, BISIP_EUNSUPPORTED, "chain exceeds the 2^31 items of one sort");
     p.items = p.n * p.columns;
     p.m_max = 0;
     for (int w = 0; w < n_windows; ++w) {
         if (windows[w] < 1 || windows[w] > p.n - 1)
-            HDI_REFUSE(BISIP_EINVAL, "window %d of %lld steps outside [1, N - 1], N = %lld", w, (long long)windows[w], p.n);
+            return refuse(v, BISIP_EINVAL, "window %d of %lld steps outside [1, N - 1], N = %lld", w, (long long)windows[w], p.n);
         const long long m = p.n - windows[w];
         p.m_max = m > p.m_max ? m : p.m_max;
     }
@@ -217,8 +215,8 @@ int make_plan(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemb
         p.temp_bytes = sort_scratch_bound(p.items, p.columns);
         p.need = 2 * p.col_bytes + align256(p.temp_bytes);
     } else {
-        if (2 * p.columns * p.m_max > 0x7fffffffLL)
-            HDI_REFUSE(BISIP_EUNSUPPORTED, "tails of %lld values exceed the 2^31 items of one sort", 2 * p.columns * p.m_max);
+        if (2 * p.columns * p.m_max > GRID_MAX)
+            return refuse(v, BISIP_EUNSUPPORTED, "tails of %lld values exceed the 2^31 items of one sort", 2 * p.columns * p.m_max);
         p.temp_bytes = sort_scratch_bound(2 * p.columns * p.m_max, 2 * p.columns);
         p.thr_bytes = align256((size_t)(2 * n_windows) * p.columns * 8);
         p.count_bytes = align256((size_t)2 * p.columns * 4);
@@ -226,7 +224,6 @@ int make_plan(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemb
         p.tail_bytes = align256((size_t)2 * p.columns * p.m_max * 8);
         p.need = p.col_bytes + p.thr_bytes + p.count_bytes + p.flag_bytes + 2 * p.tail_bytes + align256(p.temp_bytes);
     }
-#undef HDI_REFUSE
     return BISIP_OK;
 }
 
@@ -238,7 +235,7 @@ int64_t bisip_chain_hdi_workspace(int64_t n_samples, int64_t n_ensembles, int64_
                                   int n_windows, const int64_t *windows)
 {
     HdiPlan p{};
-    if (make_plan(n_samples, n_ensembles, walkers_per_ensemble, ndim, n_windows, windows, p, true) != BISIP_OK) return -1;
+    if (make_plan(n_samples, n_ensembles, walkers_per_ensemble, ndim, n_windows, windows, p, QUIET) != BISIP_OK) return -1;
     return (int64_t)p.need;
 }
 
@@ -248,16 +245,13 @@ int bisip_chain_hdi_dev(const double *d_chain, int64_t n_samples, int64_t sample
 {
     if (!d_chain || !windows || !d_out || !d_work) return fail(BISIP_EINVAL, "null argument");
     HdiPlan p{};
-    int rc = make_plan(n_samples, n_ensembles, walkers_per_ensemble, ndim, n_windows, windows, p, false);
-    if (rc != BISIP_OK) return rc;
-    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
-    if (work_bytes < (int64_t)p.need)
-        return fail(BISIP_EINVAL, "workspace of %lld bytes, need %zu", (long long)work_bytes, p.need);
+    BISIP_TRY(make_plan(n_samples, n_ensembles, walkers_per_ensemble, ndim, n_windows, windows, p, LOUD));
+    BISIP_TRY(check_stride({n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim}));
+    BISIP_TRY(check_workspace(d_work, work_bytes, (int64_t)p.need));
     hipStream_t st = (hipStream_t)stream;
     char *base = (char *)d_work;
     double *cols = (double *)base;
-    rc = gather_columns(d_chain, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, cols, st);
+    int rc = gather_columns(d_chain, n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, cols, st);
     if (rc != BISIP_OK) return rc;
 
     WindowArgs wa{};

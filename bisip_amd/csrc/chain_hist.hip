@@ -264,21 +264,17 @@ struct PairHistLaunch {
     }
 };
 
+// no count is capped: chain_splits keeps the parts of an ensemble within one grid, hist_grid holds the ensembles to it
 int check_hist_chain(int64_t n_samples, int64_t sample_stride, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim)
 {
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
-    if (n_samples < 1 || n_ensembles < 1 || walkers_per_ensemble < 1) return fail(BISIP_EINVAL, "bad chain shape");
-    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
-    return BISIP_OK;
+    return check_chain({n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim}, 1, NO_CAP, NO_CAP, NO_CAP);
 }
 
 int hist_grid(HistArgs &a, long long wanted, unsigned *gx)
 {
     const ChainSplit sp = chain_splits(a.n_samples, a.E, a.Wp, wanted);
     a.ss = sp.ss; a.sw = sp.sw;
-    if (a.E > 0x7fffffffLL / (sp.ss * sp.sw))
-        return fail(BISIP_EUNSUPPORTED, "%lld ensembles in %lld x %lld parts exceed one grid", a.E, sp.ss, sp.sw);
+    BISIP_TRY(check_grid(a.E, sp.ss * sp.sw, LOUD, "%lld ensembles in %lld x %lld parts", a.E, sp.ss, sp.sw));
     *gx = (unsigned)(a.E * sp.ss * sp.sw);
     return BISIP_OK;
 }
@@ -291,15 +287,13 @@ int bisip_chain_range_dev(const double *d_chain, int64_t n_samples, int64_t samp
                           int64_t walkers_per_ensemble, int ndim, double *d_out, int64_t *d_nonfinite, void *stream)
 {
     if (!d_chain || !d_out || !d_nonfinite) return fail(BISIP_EINVAL, "null argument");
-    int rc = check_hist_chain(n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim);
-    if (rc != BISIP_OK) return rc;
+    BISIP_TRY(check_hist_chain(n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim));
     HistArgs a{};
     a.chain = d_chain; a.n_samples = n_samples; a.sample_stride = sample_stride;
     a.E = n_ensembles; a.Wp = walkers_per_ensemble; a.ndim = ndim;
     a.keys = (unsigned long long *)d_out; a.nonfinite = (unsigned long long *)d_nonfinite;
     unsigned gx = 0;
-    rc = hist_grid(a, 4096, &gx);
-    if (rc != BISIP_OK) return rc;
+    BISIP_TRY(hist_grid(a, 4096, &gx));
     hipStream_t st = (hipStream_t)stream;
     const dim3 cols((unsigned)((n_ensembles * ndim + 255) / 256));
     hipLaunchKernelGGL(k_chain_range_init, cols, dim3(256), 0, st, a);
@@ -314,8 +308,7 @@ int bisip_chain_histograms_dev(const double *d_chain, int64_t n_samples, int64_t
                                int64_t *d_counts, void *stream)
 {
     if (!d_chain || !d_edges || !d_counts) return fail(BISIP_EINVAL, "null argument");
-    int rc = check_hist_chain(n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim);
-    if (rc != BISIP_OK) return rc;
+    BISIP_TRY(check_hist_chain(n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim));
     if (bins < 1) return fail(BISIP_EINVAL, "bins=%d", bins);
     const size_t lds = (size_t)ndim * ((size_t)(bins + 1) * 8 + (size_t)bins * 4);
     if (lds > HIST_LDS_BYTES)
@@ -326,8 +319,7 @@ int bisip_chain_histograms_dev(const double *d_chain, int64_t n_samples, int64_t
     a.E = n_ensembles; a.Wp = walkers_per_ensemble; a.ndim = ndim; a.bins = bins;
     a.edges = d_edges; a.counts = (unsigned long long *)d_counts;
     unsigned gx = 0;
-    rc = hist_grid(a, 4096, &gx);
-    if (rc != BISIP_OK) return rc;
+    BISIP_TRY(hist_grid(a, 4096, &gx));
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)n_ensembles * ndim * bins * 8, st));
     hipLaunchKernelGGL(k_chain_histograms, dim3(gx), dim3(256), lds, st, a);
@@ -340,8 +332,7 @@ int bisip_chain_pair_histograms_dev(const double *d_chain, int64_t n_samples, in
                                     int bins, int64_t *d_counts, void *stream)
 {
     if (!d_chain || !d_edges || !d_counts) return fail(BISIP_EINVAL, "null argument");
-    int rc = check_hist_chain(n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim);
-    if (rc != BISIP_OK) return rc;
+    BISIP_TRY(check_hist_chain(n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim));
     if (ndim < 2) return fail(BISIP_EINVAL, "ndim=%d has no pairs", ndim);
     if (bins < 1) return fail(BISIP_EINVAL, "bins=%d", bins);
     const size_t fixed = (size_t)ndim * (bins + 2) * 8, cell_bytes = (size_t)bins * bins * 4;
@@ -358,8 +349,7 @@ int bisip_chain_pair_histograms_dev(const double *d_chain, int64_t n_samples, in
     a.edges = d_edges; a.counts = (unsigned long long *)d_counts;
     unsigned gx = 0;
     // every workgroup ends with one global add per cell it touched: fewer, longer workgroups than the 1-D sweep
-    rc = hist_grid(a, 1024, &gx);
-    if (rc != BISIP_OK) return rc;
+    BISIP_TRY(hist_grid(a, 1024, &gx));
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)n_ensembles * a.npairs * cell_bytes * 2, st));
     return launch_by_ndim<PairHistLaunch>(ndim, dim3(gx, (unsigned)groups), st, a);

@@ -33,14 +33,14 @@
 //
 // The unit needs the context (the records of bisip_q_columns_dev) and so takes host.h through row_pass.h, as
 // dispatch_fit.hip does; kernels.h and chain.h both define wave_sum, so what it uses of the column toolkit (chain.h,
-// chain_columns.hip) is declared here instead of included.
+// chain_columns.hip) is declared here instead of included.  The checks and align256 come from chain_check.h.
+#include "chain_check.h"
 #include "row_pass.h"
 
 namespace bisip {
 namespace host {
 int select_columns(const double *cols, long long n, long long columns, int n_percentiles, const std::vector<long long> &lo,
                    const std::vector<double> &t, double *d_out, hipStream_t st, long long out_stride, bool raw);
-size_t align256(size_t x);
 size_t sort_scratch_bound(long long items, long long segments);
 int sort_segments(void *d_temp, size_t temp, const double *in, double *out, long long items, long long segments, long long n,
                   hipStream_t st);
@@ -272,19 +272,18 @@ struct LooPlan {
     size_t thr_bytes, count_bytes, flag_bytes, part_bytes, tail_bytes, temp_bytes, need;
 };
 
-// checks the shape; quiet: the workspace function only reports < 0
-int make_plan(int64_t n, int64_t columns, int64_t tail_len, LooPlan &p, bool quiet)
+// checks the shape; QUIET: the workspace function only reports < 0
+int make_plan(int64_t n, int64_t columns, int64_t tail_len, LooPlan &p, Voice v)
 {
-#define LOO_REFUSE(code, ...) return quiet ? (code) : fail((code), __VA_ARGS__)
-    if (n < 2 || columns < 1) LOO_REFUSE(BISIP_EINVAL, "bad shape: %lld columns of %lld values", (long long)columns, (long long)n);
+    if (n < 2 || columns < 1) return refuse(v, BISIP_EINVAL, "bad shape: %lld columns of %lld values", (long long)columns, (long long)n);
     if (tail_len < 1 || tail_len > n - 1)
-        LOO_REFUSE(BISIP_EINVAL, "tail_len=%lld outside [1, n - 1], n = %lld", (long long)tail_len, (long long)n);
+        return refuse(v, BISIP_EINVAL, "tail_len=%lld outside [1, n - 1], n = %lld", (long long)tail_len, (long long)n);
     if (tail_len > LOO_MAX_TAIL)
-        LOO_REFUSE(BISIP_EUNSUPPORTED, "tail_len=%lld: more than %d profile points", (long long)tail_len, LOO_MAX_M);
+        return refuse(v, BISIP_EUNSUPPORTED, "tail_len=%lld: more than %d profile points", (long long)tail_len, LOO_MAX_M);
     if (columns > 0x7fffffffLL || columns * tail_len > 0x7fffffffLL)
-        LOO_REFUSE(BISIP_EUNSUPPORTED, "tails of %lld values exceed the 2^31 items of one sort", (long long)(columns * tail_len));
+        return refuse(v, BISIP_EUNSUPPORTED, "tails of %lld values exceed the 2^31 items of one sort", (long long)(columns * tail_len));
     p.chunks = (n + LOO_CHUNK - 1) / LOO_CHUNK;
-    if (p.chunks > 0x7fffffffLL / columns) LOO_REFUSE(BISIP_EUNSUPPORTED, "%lld chunks of %lld columns exceed one grid", p.chunks, (long long)columns);
+    BISIP_TRY(check_grid(p.chunks, columns, v, "%lld chunks of %lld columns", p.chunks, (long long)columns));
     p.thr_bytes = align256((size_t)2 * columns * 8);
     p.count_bytes = align256((size_t)columns * 4);
     p.flag_bytes = align256((size_t)columns * 4);
@@ -292,7 +291,6 @@ int make_plan(int64_t n, int64_t columns, int64_t tail_len, LooPlan &p, bool qui
     p.tail_bytes = align256((size_t)columns * tail_len * 8);
     p.temp_bytes = sort_scratch_bound(columns * tail_len, columns);
     p.need = p.thr_bytes + p.count_bytes + p.flag_bytes + p.part_bytes + 2 * p.tail_bytes + align256(p.temp_bytes);
-#undef LOO_REFUSE
     return BISIP_OK;
 }
 
@@ -315,7 +313,7 @@ int bisip_q_columns_dev(bisip_ctx *c, int64_t first_spectrum, int64_t n_spectra,
     a.N = c->N; a.rec = (int)(c->cb_stride / c->N);
     a.cb = c->d_cb + first_spectrum * c->cb_stride; a.cb_stride = c->cb_stride;
     const long long columns = n_spectra * 2 * c->N;
-    if (a.chunks > 0x7fffffffLL / columns) return fail(BISIP_EUNSUPPORTED, "%lld chunks of %lld columns exceed one grid", a.chunks, columns);
+    BISIP_TRY(check_grid(a.chunks, columns, LOUD, "%lld chunks of %lld columns", a.chunks, columns));
     HIP_TRY(hipSetDevice(c->device));
     hipLaunchKernelGGL(k_q_columns, dim3((unsigned)(columns * a.chunks)), dim3(LOO_THREADS), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
@@ -325,7 +323,7 @@ int bisip_q_columns_dev(bisip_ctx *c, int64_t first_spectrum, int64_t n_spectra,
 int64_t bisip_loo_columns_workspace(int64_t n, int64_t columns, int64_t tail_len)
 {
     LooPlan p{};
-    if (make_plan(n, columns, tail_len, p, true) != BISIP_OK) return -1;
+    if (make_plan(n, columns, tail_len, p, QUIET) != BISIP_OK) return -1;
     return (int64_t)p.need;
 }
 
@@ -335,10 +333,8 @@ int bisip_loo_columns_dev(const double *d_q, int64_t n, int64_t columns, int64_t
     if (!d_q || !d_work) return fail(BISIP_EINVAL, "null argument");
     if (!d_elpd_rel && !d_khat && !d_sigma && !d_ntail) return fail(BISIP_EINVAL, "no output asked for");
     LooPlan p{};
-    int rc = make_plan(n, columns, tail_len, p, false);
-    if (rc != BISIP_OK) return rc;
-    if (work_bytes < (int64_t)p.need)
-        return fail(BISIP_EINVAL, "workspace of %lld bytes, need %zu", (long long)work_bytes, p.need);
+    BISIP_TRY(make_plan(n, columns, tail_len, p, LOUD));
+    BISIP_TRY(check_workspace(d_work, work_bytes, (int64_t)p.need));
     if (((uintptr_t)d_q % 8) || ((uintptr_t)d_work % 8) || ((uintptr_t)d_elpd_rel % 8) || ((uintptr_t)d_khat % 8) ||
         ((uintptr_t)d_sigma % 8) || ((uintptr_t)d_ntail % 8))
         return fail(BISIP_EINVAL, "buffers must be 8-byte aligned");
@@ -355,7 +351,7 @@ int bisip_loo_columns_dev(const double *d_q, int64_t n, int64_t columns, int64_t
     // u = s[n - tail_len - 1] and qmax = s[n - 1], the order statistics themselves
     const std::vector<long long> lo{n - tail_len - 1, n - 1};
     const std::vector<double> t{0.0, 0.0};
-    rc = select_columns(d_q, n, columns, 2, lo, t, thr, st, columns, true);
+    int rc = select_columns(d_q, n, columns, 2, lo, t, thr, st, columns, true);
     if (rc != BISIP_OK) return rc;
     HIP_TRY(hipMemsetAsync(count, 0, p.count_bytes + p.flag_bytes, st));      // (count and flag lie side by side)
 

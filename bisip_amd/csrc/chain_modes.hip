@@ -5,6 +5,7 @@
 // mode_order_row<K> (mode_order.h) for both; the definitions are in the module docstring of bisip_amd/modes.py.  The
 // ordered rows are a chain of ndim = 1 + 3K and the descriptors one of ndim = 1 + 2K that the moments, percentiles and
 // HDI summarise.
+#include "chain_check.h"
 #include "host.h"
 #include "mode_order.h"
 
@@ -66,12 +67,10 @@ int check_mode_order_args(const void *chain, int64_t n_samples, int64_t sample_s
         return fail(BISIP_EINVAL, "n_modes=%d out of range [1, %d]", n_modes, BISIP_MAX_MODES);
     if (key_group < MODE_KEY_M || key_group > MODE_KEY_C)
         return fail(BISIP_EINVAL, "key_group=%d (0: m, 1: log_tau, 2: c)", key_group);
-    if (n_samples < 1 || n_ensembles < 1 || walkers_per_ensemble < 1) return fail(BISIP_EINVAL, "bad chain shape");
-    if (sample_stride < n_ensembles * walkers_per_ensemble * (1 + 3 * n_modes))
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
-    if (n_ensembles * walkers_per_ensemble > 0x7fffffffLL)
-        return fail(BISIP_EUNSUPPORTED, "%lld rows per sample exceed 2^31", (long long)(n_ensembles * walkers_per_ensemble));
-    return BISIP_OK;
+    const ChainShape s{n_samples, sample_stride, n_ensembles, walkers_per_ensemble, 1 + 3 * n_modes};     // (ndim: n_modes is checked)
+    BISIP_TRY(check_counts(s, NO_CAP, NO_CAP, NO_CAP));
+    BISIP_TRY(check_stride(s));
+    return check_rows(s);
 }
 
 }  // namespace

@@ -178,6 +178,9 @@ static int moment_splits(int64_t n_samples, int64_t E)
     return (int)(s < 1 ? 1 : s);
 }
 
+// E: grid dimension x of the partial sums.  Neither n nor Wp is capped: the kernels index both in 64 bits.
+static int check_moments_chain(const ChainShape &s) { return check_chain(s, 1, NO_CAP, GRID_MAX, NO_CAP); }
+
 extern "C" {
 
 int64_t bisip_chain_moments_workspace(int64_t n_samples, int64_t n_ensembles, int ndim)
@@ -191,11 +194,7 @@ int bisip_chain_moments_dev(const double *d_chain, int64_t n_samples, int64_t sa
                             double *d_mean, double *d_std, double *d_work, void *stream)
 {
     if (!d_chain || !d_mean || !d_std || !d_work) return fail(BISIP_EINVAL, "null argument");
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
-    if (n_samples < 1 || n_ensembles < 1 || n_ensembles > 0x7fffffffLL || walkers_per_ensemble < 1)
-        return fail(BISIP_EINVAL, "bad chain shape");
-    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
+    BISIP_TRY(check_moments_chain({n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim}));
     MomentArgs a;
     a.chain = d_chain; a.n_samples = n_samples; a.sample_stride = sample_stride;
     a.E = n_ensembles; a.Wp = walkers_per_ensemble; a.ndim = ndim;
@@ -222,11 +221,7 @@ int bisip_chain_central_moments_dev(const double *d_chain, int64_t n_samples, in
                                     const double *d_center, double *d_m2, double *d_m4, double *d_work, void *stream)
 {
     if (!d_chain || !d_center || !d_m2 || !d_m4 || !d_work) return fail(BISIP_EINVAL, "null argument");
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
-    if (n_samples < 1 || n_ensembles < 1 || n_ensembles > 0x7fffffffLL || walkers_per_ensemble < 1)
-        return fail(BISIP_EINVAL, "bad chain shape");
-    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
+    BISIP_TRY(check_moments_chain({n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim}));
     CentralArgs a;
     a.chain = d_chain; a.n_samples = n_samples; a.sample_stride = sample_stride;
     a.E = n_ensembles; a.Wp = walkers_per_ensemble; a.ndim = ndim;

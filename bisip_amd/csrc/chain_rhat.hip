@@ -205,15 +205,15 @@ __global__ __launch_bounds__(1024) void k_rhat_fused(const RhatArgs a)
     if (lane == 0) a.rhat[e * a.ndim + q] = r;
 }
 
-int check_rhat_shape(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim, int splits)
+// E: grid dimension x of the fused and the R-hat kernels; Wp: Wp * ndim and splits * Wp * ndim are ints in the kernels
+// (2 * BISIP_MAX_NDIM columns per walker at most).  n has a rule of its own, which comes after the counts.
+int check_rhat_shape(const ChainShape &s, int splits, Voice v)
 {
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
-    if (splits != 1 && splits != 2) return fail(BISIP_EINVAL, "splits=%d: 1 or 2", splits);
-    if (n_ensembles < 1 || walkers_per_ensemble < 1 || walkers_per_ensemble > 0x7fffffffLL / (2 * BISIP_MAX_NDIM) ||
-        n_ensembles > 0x7fffffffLL)
-        return fail(BISIP_EINVAL, "bad chain shape");
-    if (n_samples < 2 * splits) return fail(BISIP_EINVAL, "n_samples=%lld: a chain needs 2 samples, a half too", (long long)n_samples);
-    if (splits * walkers_per_ensemble < 2) return fail(BISIP_EINVAL, "R-hat needs 2 chains");
+    BISIP_TRY(check_ndim(s.ndim, 1, v));
+    if (splits != 1 && splits != 2) return refuse(v, BISIP_EINVAL, "splits=%d: 1 or 2", splits);
+    BISIP_TRY(check_counts({1, 0, s.E, s.Wp, s.ndim}, NO_CAP, GRID_MAX, GRID_MAX / (2 * BISIP_MAX_NDIM), v));
+    if (s.n < 2 * splits) return refuse(v, BISIP_EINVAL, "n_samples=%lld: a chain needs 2 samples, a half too", (long long)s.n);
+    if (splits * s.Wp < 2) return refuse(v, BISIP_EINVAL, "R-hat needs 2 chains");
     return BISIP_OK;
 }
 
@@ -223,7 +223,7 @@ extern "C" {
 
 int64_t bisip_chain_rhat_workspace(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim, int splits)
 {
-    if (check_rhat_shape(n_samples, n_ensembles, walkers_per_ensemble, ndim, splits) != BISIP_OK) return -1;
+    if (check_rhat_shape({n_samples, 0, n_ensembles, walkers_per_ensemble, ndim}, splits, QUIET) != BISIP_OK) return -1;
     const RhatPlan p = rh_plan(n_samples, n_ensembles, walkers_per_ensemble, ndim, splits);
     if ((p.C + RH_THREADS - 1) / RH_THREADS > 0x7fffffffLL) return -1;
     if (p.fused) return 0;
@@ -237,13 +237,12 @@ int bisip_chain_rhat_dev(const double *d_chain, int64_t n_samples, int64_t sampl
 {
     if (!d_chain) return fail(BISIP_EINVAL, "null argument");
     if (!d_mean && !d_var && !d_rhat) return fail(BISIP_EINVAL, "none of mean, variance and R-hat asked for");
-    int rc = check_rhat_shape(n_samples, n_ensembles, walkers_per_ensemble, ndim, splits);
-    if (rc != BISIP_OK) return rc;
-    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
+    const ChainShape s{n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim};
+    BISIP_TRY(check_rhat_shape(s, splits, LOUD));
+    BISIP_TRY(check_stride(s));
     const RhatPlan p = rh_plan(n_samples, n_ensembles, walkers_per_ensemble, ndim, splits);
     const long long tiles = (p.C + RH_THREADS - 1) / RH_THREADS;
-    if (tiles > 0x7fffffffLL) return fail(BISIP_EUNSUPPORTED, "%lld columns exceed one grid", p.C);
+    BISIP_TRY(check_grid(tiles, 1, LOUD, "%lld columns", p.C));
     hipStream_t st = (hipStream_t)stream;
     RhatArgs a{};
     a.chain = d_chain; a.stride = sample_stride; a.E = n_ensembles; a.C = p.C; a.L = p.L; a.start1 = p.start1;
@@ -258,9 +257,7 @@ int bisip_chain_rhat_dev(const double *d_chain, int64_t n_samples, int64_t sampl
         return BISIP_OK;
     }
 
-    const long long need = bisip_chain_rhat_workspace(n_samples, n_ensembles, walkers_per_ensemble, ndim, splits);
-    if (!d_work || work_bytes < need)
-        return fail(BISIP_EINVAL, "workspace of %lld bytes, need %lld", (long long)(d_work ? work_bytes : 0), need);
+    BISIP_TRY(check_workspace(d_work, work_bytes, bisip_chain_rhat_workspace(n_samples, n_ensembles, walkers_per_ensemble, ndim, splits)));
     double *w = (double *)d_work;
     if (d_rhat) {                                 // the R-hat stage reads the moments of every chain
         if (!a.mean) a.mean = w;

@@ -106,17 +106,6 @@ struct ColumnsLaunch {
     }
 };
 
-int check_rtd_chain(int64_t n_samples, int64_t sample_stride, int64_t n_ensembles, int64_t walkers_per_ensemble,
-                    int ndim, int64_t rows)
-{
-    if (ndim < 2 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range (r0 and a_0 at least)", ndim);
-    if (n_samples < 1 || n_ensembles < 1 || walkers_per_ensemble < 1) return fail(BISIP_EINVAL, "bad chain shape");
-    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
-    if (rows > 0x7fffffffLL) return fail(BISIP_EUNSUPPORTED, "%lld rows per sample exceed 2^31", (long long)rows);
-    return BISIP_OK;
-}
-
 // x: the rows of one sample; y: samples, a grid-stride loop beyond 65535
 dim3 rtd_grid(int64_t rows, int64_t n_samples)
 {
@@ -132,9 +121,11 @@ int bisip_rtd_integrals_dev(const double *d_chain, int64_t n_samples, int64_t sa
                             const double *d_norm_factor, double *d_out, void *stream)
 {
     if (!d_chain || !d_power_sums || !d_norm_factor || !d_out) return fail(BISIP_EINVAL, "null argument");
+    // no count is capped as a bad shape: the rows of a sample beyond 32 bits are unsupported, and reported after the stride
+    const ChainShape s{n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim};
+    BISIP_TRY(check_chain(s, 2, NO_CAP, NO_CAP, NO_CAP));
+    BISIP_TRY(check_rows(s));
     const int64_t rows = n_ensembles * walkers_per_ensemble;
-    int rc = check_rtd_chain(n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, rows);
-    if (rc != BISIP_OK) return rc;
     const RtdIntegralArgs a{d_chain, n_samples, sample_stride, (unsigned)rows, (unsigned)walkers_per_ensemble,
                             d_power_sums, d_norm_factor, d_out};
     return launch_by_ndim<IntegralsLaunch>(ndim, rtd_grid(rows, n_samples), (hipStream_t)stream, a);
@@ -149,11 +140,11 @@ int bisip_rtd_columns_dev(const double *d_chain, int64_t n_samples, int64_t samp
     if (first_ensemble < 0 || count < 1 || first_ensemble + count > n_ensembles)
         return fail(BISIP_EINVAL, "ensembles [%lld, %lld) outside [0, %lld)", (long long)first_ensemble,
                     (long long)(first_ensemble + count), (long long)n_ensembles);
-    if (n_ensembles * walkers_per_ensemble > 0x7fffffffLL)
-        return fail(BISIP_EUNSUPPORTED, "%lld rows per sample exceed 2^31", (long long)(n_ensembles * walkers_per_ensemble));
+    // the rows of the whole sample come before the shape here, and cover the count * Wp rows the kernel numbers
+    const ChainShape s{n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim};
+    BISIP_TRY(check_rows(s));
+    BISIP_TRY(check_chain(s, 2, NO_CAP, NO_CAP, NO_CAP));
     const int64_t rows = count * walkers_per_ensemble;
-    int rc = check_rtd_chain(n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim, rows);
-    if (rc != BISIP_OK) return rc;
     const RtdColumnArgs a{d_chain, n_samples, sample_stride, (unsigned)rows, (unsigned)walkers_per_ensemble,
                           first_ensemble, n_tau, d_log_tau, d_cols};
     return launch_by_ndim<ColumnsLaunch>(ndim, rtd_grid(rows, n_samples), (hipStream_t)stream, a);

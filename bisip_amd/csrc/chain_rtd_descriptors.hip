@@ -68,13 +68,9 @@ int check_descriptor_args(const void *chain, const void *log_tau, const void *q,
     if (!chain || !log_tau || !q || !out) return fail(BISIP_EINVAL, "null argument");
     if (n_tau < 1) return fail(BISIP_EINVAL, "n_tau=%d", n_tau);
     if (n_q < 1 || n_q > RTD_MAX_FRACTIONS) return fail(BISIP_EINVAL, "n_q=%d out of range [1, %d]", n_q, RTD_MAX_FRACTIONS);
-    if (ndim < 2 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range (r0 and a_0 at least)", ndim);
-    if (n_samples < 1 || n_ensembles < 1 || walkers_per_ensemble < 1) return fail(BISIP_EINVAL, "bad chain shape");
-    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
-    if (n_ensembles * walkers_per_ensemble > 0x7fffffffLL)
-        return fail(BISIP_EUNSUPPORTED, "%lld rows per sample exceed 2^31", (long long)(n_ensembles * walkers_per_ensemble));
-    return BISIP_OK;
+    const ChainShape s{n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim};
+    BISIP_TRY(check_chain(s, 2, NO_CAP, NO_CAP, NO_CAP));      // (as bisip_rtd_integrals_dev: the rows come after the stride)
+    return check_rows(s);
 }
 
 }  // namespace
@@ -104,7 +100,7 @@ int bisip_rtd_descriptors_host(const double *chain, int64_t n_samples, int64_t s
     if (rc != BISIP_OK) return rc;
     if (!rtd_descriptor_rows_host_by_ndim<BISIP_MAX_NDIM>(ndim, chain, n_samples, sample_stride,
                                                           n_ensembles * walkers_per_ensemble, log_tau, n_tau, q, n_q, out))
-        return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
+        return fail(BISIP_EINVAL, "no row function of ndim=%d", ndim);      // (check_descriptor_args has checked ndim)
     return BISIP_OK;
 }
 

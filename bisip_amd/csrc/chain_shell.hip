@@ -333,9 +333,9 @@ int bisip_chain_shell_rows_dev(const double *d_chain, const double *d_logp, int6
                                void *d_work, void *stream)
 {
     if (!d_chain || !d_logp || !d_out || !d_work) return fail(BISIP_EINVAL, "null argument");
-    if (n_samples < 1 || n_ensembles < 1 || n_ensembles > 0x7fffffffLL || walkers_per_ensemble < 1)
-        return fail(BISIP_EINVAL, "bad chain shape");
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
+    // the counts before ndim here; E: a workgroup per ensemble along one grid dimension.  There is no stride: the chain and logp are contiguous.
+    BISIP_TRY(check_counts({n_samples, 0, n_ensembles, walkers_per_ensemble, ndim}, NO_CAP, GRID_MAX, NO_CAP));
+    BISIP_TRY(check_ndim(ndim));
     if (k < 1 || k > (1 << 20) || n_stride < 0 || n_stride > TPB || n_stride > walkers_per_ensemble)
         return fail(BISIP_EINVAL, "k=%d / n_stride=%d out of range", k, n_stride);
     if (n_samples * walkers_per_ensemble > 0x7fffffffLL) return fail(BISIP_EUNSUPPORTED, "more than 2^31 samples per ensemble");

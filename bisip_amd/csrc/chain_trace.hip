@@ -210,15 +210,13 @@ long long slab_samples(long long n, long long E, long long Wp, int ndim)
     return S < n ? S : n;
 }
 
-int check_trace_shape(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim, int n_percentiles)
+// Wp: an int in TraceArgs; E: 32 bits too; n is not capped here: each path holds its samples to one grid further down
+int check_trace_shape(const ChainShape &s, int n_percentiles, Voice v)
 {
-    if (ndim < 1 || ndim > BISIP_MAX_NDIM) return fail(BISIP_EINVAL, "ndim=%d out of range", ndim);
+    BISIP_TRY(check_ndim(s.ndim, 1, v));
     if (n_percentiles < 0 || n_percentiles > TR_MAX_P)
-        return fail(BISIP_EINVAL, "n_percentiles=%d: 0 ... %d per call", n_percentiles, TR_MAX_P);
-    if (n_samples < 1 || n_ensembles < 1 || walkers_per_ensemble < 1 || walkers_per_ensemble > 0x7fffffffLL ||
-        n_ensembles > 0x7fffffffLL)
-        return fail(BISIP_EINVAL, "bad chain shape");
-    return BISIP_OK;
+        return refuse(v, BISIP_EINVAL, "n_percentiles=%d: 0 ... %d per call", n_percentiles, TR_MAX_P);
+    return check_counts(s, NO_CAP, GRID_MAX, GRID_MAX, v);
 }
 
 }  // namespace
@@ -234,7 +232,7 @@ int bisip_chain_trace_lds_walkers(int ndim)
 int64_t bisip_chain_trace_workspace(int64_t n_samples, int64_t n_ensembles, int64_t walkers_per_ensemble, int ndim,
                                     int n_percentiles)
 {
-    if (check_trace_shape(n_samples, n_ensembles, walkers_per_ensemble, ndim, n_percentiles) != BISIP_OK) return -1;
+    if (check_trace_shape({n_samples, 0, n_ensembles, walkers_per_ensemble, ndim}, n_percentiles, QUIET) != BISIP_OK) return -1;
     if (walkers_per_ensemble <= lds_walkers(ndim)) return 0;
     const long long S = slab_samples(n_samples, n_ensembles, walkers_per_ensemble, ndim);
     if (S < 1) return -1;
@@ -246,15 +244,14 @@ int bisip_chain_trace_dev(const double *d_chain, int64_t n_samples, int64_t samp
                           double *d_pct, double *d_mean, void *d_work, int64_t work_bytes, void *stream)
 {
     if (!d_chain || (n_percentiles > 0 && (!percentiles || !d_pct))) return fail(BISIP_EINVAL, "null argument");
-    int rc = check_trace_shape(n_samples, n_ensembles, walkers_per_ensemble, ndim, n_percentiles);
-    if (rc != BISIP_OK) return rc;
-    if (sample_stride < n_ensembles * walkers_per_ensemble * ndim)
-        return fail(BISIP_EINVAL, "sample_stride smaller than one sample");
+    const ChainShape s{n_samples, sample_stride, n_ensembles, walkers_per_ensemble, ndim};
+    BISIP_TRY(check_trace_shape(s, n_percentiles, LOUD));
+    BISIP_TRY(check_stride(s));
     if (n_percentiles == 0 && !d_mean) return fail(BISIP_EINVAL, "neither percentiles nor the mean asked for");
     const long long E = n_ensembles, Wp = walkers_per_ensemble;
     std::vector<long long> lo(n_percentiles);
     std::vector<double> t(n_percentiles);
-    rc = percentile_ranks(Wp, percentiles, n_percentiles, lo, t);
+    int rc = percentile_ranks(Wp, percentiles, n_percentiles, lo, t);
     if (rc != BISIP_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
 
@@ -273,8 +270,7 @@ int bisip_chain_trace_dev(const double *d_chain, int64_t n_samples, int64_t samp
         a.pct = d_pct; a.mean = d_mean;
         const size_t lds = (size_t)G * ndim * a.pitch * 8;
         if (lds > TR_LDS_BYTES) return fail(BISIP_EHIP, "trace columns of %zu bytes exceed the LDS of a workgroup", lds);
-        if (a.groups > 0x7fffffffLL / n_samples)
-            return fail(BISIP_EUNSUPPORTED, "%lld samples x %lld workgroups exceed one grid", (long long)n_samples, a.groups);
+        BISIP_TRY(check_grid(a.groups, n_samples, LOUD, "%lld samples x %lld workgroups", (long long)n_samples, a.groups));
         hipLaunchKernelGGL(k_chain_trace_lds, dim3((unsigned)(n_samples * a.groups)), dim3(TR_THREADS), lds, st, a);
         HIP_TRY(hipGetLastError());
         return BISIP_OK;
@@ -283,8 +279,7 @@ int bisip_chain_trace_dev(const double *d_chain, int64_t n_samples, int64_t samp
     const long long S = slab_samples(n_samples, E, Wp, ndim);
     if (S < 1) return fail(BISIP_EUNSUPPORTED, "one sample of %lld x %lld walkers exceeds one grid", E, Wp);
     const long long per_sample = E * Wp * ndim, out_per_sample = E * ndim;
-    if (!d_work || work_bytes < S * per_sample * 8)
-        return fail(BISIP_EINVAL, "workspace of %lld bytes, need %lld", (long long)(d_work ? work_bytes : 0), S * per_sample * 8);
+    BISIP_TRY(check_workspace(d_work, work_bytes, S * per_sample * 8));
     double *cols = (double *)d_work;
     for (long long s0 = 0; s0 < n_samples; s0 += S) {
         const long long Sb = n_samples - s0 < S ? n_samples - s0 : S, columns = Sb * out_per_sample;
