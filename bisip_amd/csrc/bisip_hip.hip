@@ -4,7 +4,6 @@
 #include <cstdlib>
 
 #include "host.h"
-#include "host_precompute.h"
 
 #include <atomic>
 #include <exception>
@@ -74,6 +73,9 @@ BatchArgs make_batch_args(const bisip_ctx *c, const double *theta, double *out, 
 }  // namespace bisip
 
 namespace {
+
+// the larger of a running worst value and x, where NaN counts as worst
+inline double worse(double worst, double x) { return x <= worst ? worst : x; }
 
 int upload(double **dst, const std::vector<double> &src)
 {
@@ -161,14 +163,14 @@ static int bound_flags(const bisip_ctx *c)
         for (int i = 0; i < D; ++i) {
             const double llo = lo[1 + D + i], lhi = hi[1 + D + i], clo = lo[1 + 2 * D + i], chi = hi[1 + 2 * D + i];
             const double y = mag(clo, chi) * (lw + mag(llo, lhi)) * LOG2E;
-            ymax = y <= ymax ? ymax : y;                  // NaN (a NaN bound) propagates as "unbounded"
+            ymax = worse(ymax, y);                        // NaN (a NaN bound) propagates as "unbounded"
             ok = ok && clo >= 0.0 && chi <= 1.0;
         }
     } else if (c->model_id == BISIP_MODEL_SHIN2015) {
         for (int i = 0; i < 2; ++i) {
             const double rlo = lo[i], rhi = hi[i], qlo = lo[2 + i], qhi = hi[2 + i], nlo = lo[4 + i], nhi = hi[4 + i];
             const double y = (mag(nlo, nhi) * lw + mag(qlo, qhi)) * LOG2E;
-            ymax = y <= ymax ? ymax : y;
+            ymax = worse(ymax, y);
             ok = ok && rlo >= 0.0 && rhi <= 1.0 && nlo >= 0.0 && nhi <= 1.0;
         }
     } else if (c->model_id == BISIP_MODEL_DIAS2000) {
@@ -194,9 +196,6 @@ static int bound_flags(const bisip_ctx *c)
     return c->grid_ok && terms <= GRID_MAX_TERMS ? (BOUNDS_FAST | BOUNDS_GRID) : BOUNDS_FAST;
 }
 
-// PolynomialDecomposition, reduced form: (re)choose the expansion point bhat for the current
-// prior box (host_precompute.h:reduced_center), record the kernel's estimated rounding error,
-// refresh the kernarg copy of spectrum 0 and the device copies of a batch.
 // the open-box prior of SURVEY.md §8 a2 on the host (rows outside it never reach a formulation)
 static bool in_prior_host(const double *th, const bisip_ctx *c)
 {
@@ -205,12 +204,6 @@ static bool in_prior_host(const double *th, const bisip_ctx *c)
     return true;
 }
 
-// Only what the current variant can run is (re)computed -- the probing is most of what a batch context costs
-// to build.  Tier 0 (plain) for every spectrum under AUTO / REDUCED.  Tier 1 (compensated: operands from a QR
-// in binary128, built on demand) for every spectrum under REDUCED_COMP, and under AUTO for exactly the spectra
-// whose plain estimate fails (all of them once the guard has closed the plain tier or the mix): on
-// well-conditioned designs -- every bundled spectrum, the headline shape -- the compensated tier is never looked
-// at.  A spectrum's probe rows serve both tiers.  set_variant, set_bounds and the guard come back here.
 // Which spectra of a batch take the plain tier inside a compensated launch (host.h: tier_of, mixed).
 static int update_tiers(bisip_ctx *c)
 {
@@ -233,7 +226,9 @@ static int update_tiers(bisip_ctx *c)
     return BISIP_OK;
 }
 
-// does spectrum e run the compensated tier under the context's present variant and history?
+// Must the compensated tier of spectrum e be ESTIMATED under the context's requested variant and history?  Asked
+// while the estimates are being made, so it cannot be running_tier (host.h), which says what runs once they
+// exist: AUTO's choice there (effective_variant) reads the very errors that are folded from these estimates.
 static bool needs_comp(const bisip_ctx *c, size_t e)
 {
     if (2 * c->N < c->P + 2 && c->variant == BISIP_VARIANT_AUTO) return false;   // no triangle: AUTO runs the per-frequency form
@@ -280,92 +275,110 @@ static void make_quad_operands(bisip_ctx *c, const std::vector<int64_t> &need)
     });
 }
 
-static int recenter_reduced(bisip_ctx *c)
+// ---- recenter_reduced and its steps.  PolynomialDecomposition, reduced form: (re)choose the expansion point bhat
+// for the current prior box (host_precompute.h: reduced_center_plain / _comp), record the kernels' estimated
+// rounding error, rewrite the spectra's entries of the tiers' images and upload what a kernel reads from memory.
+// Only what the current variant can run is (re)computed -- the probing is most of what a batch context costs
+// to build.  Tier 0 (plain) for every spectrum under AUTO / REDUCED.  Tier 1 (compensated: operands from a QR
+// in binary128, built on demand) for every spectrum under REDUCED_COMP, and under AUTO for exactly the spectra
+// whose plain estimate fails (all of them once the guard has closed the plain tier or the mix): on
+// well-conditioned designs -- every bundled spectrum, the headline shape -- the compensated tier is never looked
+// at.  A spectrum's probe rows serve both tiers.  set_variant, set_bounds and the guard come back here.
+
+// a new prior box: what was estimated, centred or observed on the old one no longer holds
+static void forget_reduced_box(bisip_ctx *c)
 {
-    if (c->model_id != BISIP_MODEL_POLYDECOMP || c->reduced.empty()) return BISIP_OK;
-    const int n = c->P + 2;
-    const size_t tri = (size_t)n * (n + 1) / 2;
+    c->demoted[0] = c->demoted[1] = c->mix_off = false;
+    for (auto &t : c->red) { t.valid = false; t.err = INFINITY; t.done.assign(t.done.size(), 0); }
+}
+
+// per-tier state for E spectra; an image entry per spectrum and tier, zero until the spectrum is estimated on it
+static void size_reduced_tiers(bisip_ctx *c, const ReducedLayout &L)
+{
     const size_t E = c->reduced.size();
-    const double w_shell = reduced_shell_weight();          // read once, on this thread
-    // == sizeof(ReducedArgs<P, COMP>)/8: the compensated tier's image starts with the triangle's low word
-    // as floats, an even number of them
-    const size_t lo_floats = (tri + 1) & ~(size_t)1;
-    const size_t red_doubles[2] = {tri + 3 * (size_t)n + 1, tri + 3 * (size_t)n + 1 + lo_floats / 2};
-    // a device image of a tier's operands: every tier of a batch; of a lone spectrum its compensated tier from
-    // degree 6 on, where the bulk kernel reads the operands from memory (dispatch_logprob.hip: launch_reduced)
-    auto has_image = [&](int tier) { return c->E > 1 || (tier == 1 && c->P >= REDUCED_COMP_MEMORY_OPERANDS_FROM); };
     for (int tier = 0; tier < 2; ++tier) {
         bisip_ctx::ReducedTier &T = c->red[tier];
         if (T.done.size() != E) { T.done.assign(E, 0); T.est.assign(E, 0.0); }
-        if (has_image(tier) && T.image.size() != red_doubles[tier] * E) T.image.assign(red_doubles[tier] * E, 0.0);
+        if (T.image.size() != L.doubles(tier) * E) T.image.assign(L.doubles(tier) * E, 0.0);
     }
-    // one spectrum's entry of a tier: its image (batch) and, for spectrum 0, the kernarg copy
-    auto store = [&](int tier, size_t e, const double *Rfull, const float *Rlo_full, double rest, const double *bh,
-                     const double *ev, const double *el) {
+}
+
+// One pass over the spectra `which`, a set of probes each: the plain tier where do0 asks for it, the compensated
+// tier of the spectra known to need it.  Host threads take blocks of spectra; a spectrum's slots (est, done, its
+// image entries) have one writer.
+static void estimate_spectra(bisip_ctx *c, const ReducedLayout &L, double w_shell, const std::vector<int64_t> &which, bool do0)
+{
+    // the binary128 operands of the spectra already known to need tier 1 (under AUTO a spectrum is known
+    // to once its plain estimate has failed: those come back in a second pass)
+    std::vector<int64_t> need;
+    for (int64_t e : which)
+        if (needs_comp(c, (size_t)e) && !c->red[1].done[(size_t)e]) need.push_back(e);
+    make_quad_operands(c, need);
+    parallel_blocks((int64_t)which.size(), 4, [&](int64_t i_lo, int64_t i_hi) {
+        std::vector<double> bh(L.n), ev(L.n), el(L.n);
+        ReducedProbes probes;
+        for (int64_t i = i_lo; i < i_hi; ++i) {
+            const size_t e = (size_t)which[(size_t)i];
+            bisip::ReducedProblem &rp = c->reduced[e];
+            reduced_probes(rp, c->bounds.lo, c->bounds.hi, probes);
+            if (do0 && !c->red[0].done[e]) {
+                c->red[0].est[e] = reduced_center_plain(rp, probes, c->bounds.lo, c->bounds.hi, w_shell, bh.data(), ev.data(), el.data());
+                L.pack(0, &c->red[0].image[L.doubles(0) * e], rp.R.data(), nullptr, bh.data(), ev.data(), el.data(), rp.rest);
+                c->red[0].done[e] = 1;
+            }
+            if (rp.has_quad() && needs_comp(c, e) && !c->red[1].done[e]) {
+                c->red[1].est[e] = reduced_center_comp(rp, probes, c->bounds.lo, c->bounds.hi, w_shell, bh.data(), ev.data(), el.data());
+                L.pack(1, &c->red[1].image[L.doubles(1) * e], rp.Rc.data(), rp.Rc_lo.data(), bh.data(), ev.data(), el.data(), rp.rest_c);
+                c->red[1].done[e] = 1;
+            }
+        }
+    });
+}
+
+// a tier's error: the worst estimate among the spectra that run it
+static void fold_estimates(bisip_ctx *c, int tier)
+{
+    bisip_ctx::ReducedTier &T = c->red[tier];
+    T.valid = true;
+    T.err = 0.0;
+    for (size_t e = 0; e < T.est.size(); ++e)
+        if (tier == 0 || needs_comp(c, e)) T.err = worse(T.err, T.est[e]);
+}
+
+// The images that changed, to the device where a kernel reads them from memory.  A batch's compensated image
+// has an entry for EVERY spectrum the kernel may index: spectra on the plain tier of a mixed launch read their
+// plain operands (BatchArgs::red_plain) and leave theirs at zero.
+static int upload_reduced(bisip_ctx *c, const bool changed[2])
+{
+    HIP_TRY(hipSetDevice(c->device));
+    for (int tier = 0; tier < 2; ++tier) {
         bisip_ctx::ReducedTier &T = c->red[tier];
-        std::vector<double> Rp;
-        std::vector<float> Rlo;
-        for (int i = 0; i < n; ++i)
-            for (int j = i; j < n; ++j) {
-                Rp.push_back(Rfull[(size_t)i * n + j]);
-                if (tier == 1) Rlo.push_back(Rlo_full[(size_t)i * n + j]);
-            }
-        if (tier == 1) Rlo.resize(lo_floats, 0.0f);
-        if (e == 0) {
-            T.Rpacked = Rp; T.Rlo_packed = Rlo; T.rest = rest;
-            T.bhat.assign(bh, bh + n); T.evec.assign(ev, ev + n); T.elo.assign(el, el + n);
-        }
-        if (has_image(tier)) {  // ReducedArgs<P, COMP> image: [Rlo |] R | bhat | e | elo | rest
-            double *dst = &T.image[red_doubles[tier] * e];
-            if (tier == 1) { std::memcpy(dst, Rlo.data(), lo_floats * sizeof(float)); dst += lo_floats / 2; }
-            dst = std::copy(Rp.begin(), Rp.end(), dst);
-            dst = std::copy(bh, bh + n, dst);
-            dst = std::copy(ev, ev + n, dst);
-            dst = std::copy(el, el + n, dst);
-            *dst = rest;
-        }
-    };
-    bool changed[2] = {false, false};
-    // ---- tier 0, and tier 1 of the spectra known to need it, in one pass over the spectra (shared probes)
-    const bool want0 = (c->variant == BISIP_VARIANT_AUTO || c->variant == BISIP_VARIANT_REDUCED) && !c->red[0].valid;
-    auto pass = [&](const std::vector<int64_t> &which, bool do0) {
-        // the binary128 operands of the spectra already known to need tier 1 (under AUTO a spectrum is known
-        // to once its plain estimate has failed: those come back in a second pass)
-        std::vector<int64_t> need;
-        for (int64_t e : which)
-            if (needs_comp(c, (size_t)e) && !c->red[1].done[(size_t)e]) need.push_back(e);
-        make_quad_operands(c, need);
-        parallel_blocks((int64_t)which.size(), 4, [&](int64_t i_lo, int64_t i_hi) {
-            std::vector<double> bh(n), ev(n), el(n);
-            ReducedProbes probes;
-            for (int64_t i = i_lo; i < i_hi; ++i) {
-                const size_t e = (size_t)which[(size_t)i];
-                bisip::ReducedProblem &rp = c->reduced[e];
-                reduced_probes(rp, c->bounds.lo, c->bounds.hi, probes);
-                if (do0 && !c->red[0].done[e]) {
-                    c->red[0].est[e] = reduced_center_plain(rp, probes, c->bounds.lo, c->bounds.hi, w_shell, bh.data(), ev.data(), el.data());
-                    store(0, e, rp.R.data(), nullptr, rp.rest, bh.data(), ev.data(), el.data());
-                    c->red[0].done[e] = 1;
-                }
-                if (rp.has_quad() && needs_comp(c, e) && !c->red[1].done[e]) {
-                    c->red[1].est[e] = reduced_center_comp(rp, probes, c->bounds.lo, c->bounds.hi, w_shell, bh.data(), ev.data(), el.data());
-                    store(1, e, rp.Rc.data(), rp.Rc_lo.data(), rp.rest_c, bh.data(), ev.data(), el.data());
-                    c->red[1].done[e] = 1;
-                }
-            }
-        });
-    };
-    std::vector<int64_t> all(E);
-    for (size_t e = 0; e < E; ++e) all[e] = (int64_t)e;
-    if (want0) {
-        pass(all, true);
-        changed[0] = true;
-        c->red[0].valid = true;
-        c->red[0].err = 0.0;
-        for (double v : c->red[0].est)
-            if (!(v <= c->red[0].err)) c->red[0].err = v;
+        if (!changed[tier] || !reduced_image_on_device(c, tier)) continue;
+        if (!T.d_red) HIP_TRY(hipMalloc(&T.d_red, T.image.size() * sizeof(double)));
+        // set_bounds between launches: the copy is ordered after earlier work by the sync
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(T.d_red, T.image.data(), T.image.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    // ---- tier 1 for the spectra that turned out to need it (their plain estimate failed just now, or the
+    return BISIP_OK;
+}
+
+static int recenter_reduced(bisip_ctx *c)
+{
+    if (c->model_id != BISIP_MODEL_POLYDECOMP || c->reduced.empty()) return BISIP_OK;
+    const ReducedLayout L(c->P + 2);
+    const size_t E = c->reduced.size();
+    const double w_shell = reduced_shell_weight();          // read once, on this thread
+    size_reduced_tiers(c, L);
+    bool changed[2] = {false, false};
+    // tier 0, and tier 1 of the spectra known to need it, in one pass over all spectra
+    if ((c->variant == BISIP_VARIANT_AUTO || c->variant == BISIP_VARIANT_REDUCED) && !c->red[0].valid) {
+        std::vector<int64_t> all(E);
+        for (size_t e = 0; e < E; ++e) all[e] = (int64_t)e;
+        estimate_spectra(c, L, w_shell, all, true);
+        fold_estimates(c, 0);
+        changed[0] = true;
+    }
+    // tier 1 for the spectra that turned out to need it (their plain estimate failed just now, or the
     // variant / the guard asks for it)
     bool any_comp = false;
     std::vector<int64_t> late;
@@ -374,29 +387,14 @@ static int recenter_reduced(bisip_ctx *c)
             any_comp = true;
             if (!c->red[1].done[e]) late.push_back((int64_t)e);
         }
-    if (!late.empty()) pass(late, false);
+    if (!late.empty()) estimate_spectra(c, L, w_shell, late, false);
     if (any_comp) {
-        changed[1] = changed[1] || !late.empty() || !c->red[1].valid;
-        c->red[1].valid = true;
-        c->red[1].err = 0.0;
-        for (size_t e = 0; e < E; ++e)
-            if (needs_comp(c, e) && !(c->red[1].est[e] <= c->red[1].err)) c->red[1].err = c->red[1].est[e];
-        if (c->E == 1 && c->red[1].Rpacked.empty()) return fail(BISIP_EHIP, "internal: compensated operands missing");
+        changed[1] = !late.empty() || !c->red[1].valid;
+        fold_estimates(c, 1);
+        if (c->E == 1 && !c->red[1].done[0]) return fail(BISIP_EHIP, "internal: compensated operands missing");
     }
-    // a batch's compensated image needs an entry for EVERY spectrum the kernel may index: spectra on the plain
-    // tier of a mixed launch read their plain operands (BatchArgs::red_plain) and leave theirs at zero
-    {
-        HIP_TRY(hipSetDevice(c->device));
-        for (int tier = 0; tier < 2; ++tier) {
-            bisip_ctx::ReducedTier &T = c->red[tier];
-            if (!changed[tier] || !has_image(tier) || T.image.empty()) continue;
-            if (!T.d_red) HIP_TRY(hipMalloc(&T.d_red, T.image.size() * sizeof(double)));
-            // set_bounds between launches: the copy is ordered after earlier work by the sync
-            HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(hipMemcpy(T.d_red, T.image.data(), T.image.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-    }
-    return update_tiers(c);
+    const int rc = upload_reduced(c, changed);
+    return rc != BISIP_OK ? rc : update_tiers(c);
 }
 
 // no C++ exception may cross the C ABI: the host-side precompute allocates (std::vector)
@@ -778,7 +776,8 @@ static int build_context(bisip_ctx **out, int device, int model_id, int E, int N
     c->lconst = lconsts[0];
     if (rc == BISIP_OK) rc = upload(&c->d_cb, cb);
     if (rc == BISIP_OK && !cb_lp.empty()) rc = upload(&c->d_cb_lp, cb_lp);
-    if (rc == BISIP_OK && (E > 1 || (model_id == BISIP_MODEL_POLYDECOMP && P >= REDUCED_COMP_MEMORY_OPERANDS_FROM))) rc = upload(&c->d_lconst, lconsts);
+    // the constants a kernel reads from memory: a batch's; with a lone spectrum's compensated operands, theirs
+    if (rc == BISIP_OK && (E > 1 || (model_id == BISIP_MODEL_POLYDECOMP && reduced_image_on_device(c, 1)))) rc = upload(&c->d_lconst, lconsts);
     if (rc == BISIP_OK) rc = recenter_reduced(c);
     if (rc == BISIP_OK) {
         hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
@@ -836,9 +835,7 @@ int bisip_ctx_set_bounds(bisip_ctx *c, const double *lo, const double *hi)
     if (same) return BISIP_OK;
     for (int q = 0; q < c->ndim; ++q) { c->bounds.lo[q] = lo[q]; c->bounds.hi[q] = hi[q]; }
     c->bounds.flags = bound_flags(c);
-    c->demoted[0] = c->demoted[1] = false;                            // observed on the old box
-    c->mix_off = false;
-    for (auto &t : c->red) { t.valid = false; t.err = INFINITY; t.done.assign(t.done.size(), 0); }     // estimates and expansion points belong to the old box
+    forget_reduced_box(c);
     const int rc = guarded([&] { return recenter_reduced(c); });   // the reduced form expands about a point of the box
     c->kernel_name = name_for(c);                                  // AUTO may change formulation with the box
     return rc;
@@ -884,31 +881,21 @@ const char *bisip_ctx_kernel_name(const bisip_ctx *c) { return c ? c->kernel_nam
 double bisip_ctx_reduced_error(const bisip_ctx *c)
 {
     if (!c) return NAN;
-    const int v = effective_variant(c);
-    if (v == BISIP_VARIANT_REDUCED) return c->red[0].err;
-    if (v == BISIP_VARIANT_REDUCED_COMP && c->mixed) {           // each spectrum under the tier it runs
-        double worst = 0.0;
-        for (size_t e = 0; e < c->tier_of.size(); ++e) {
-            const double x = c->red[c->tier_of[e]].est[e];
-            if (!(x <= worst)) worst = x;
-        }
-        return worst;
-    }
-    if (v == BISIP_VARIANT_REDUCED_COMP) return c->red[1].err;
-    return c->red[0].err <= c->red[1].err ? c->red[0].err : c->red[1].err;
+    const int tier = running_tier(c, 0);
+    if (tier < 0) return c->red[0].err <= c->red[1].err ? c->red[0].err : c->red[1].err;
+    if (!c->mixed) return c->red[tier].err;
+    double worst = 0.0;                                          // each spectrum under the tier it runs
+    for (size_t e = 0; e < c->tier_of.size(); ++e) worst = worse(worst, c->red[running_tier(c, e)].est[e]);
+    return worst;
 }
 
 int bisip_ctx_reduced_tiers(const bisip_ctx *c, int64_t *n_plain, int64_t *n_comp)
 {
     if (!c || !n_plain || !n_comp) return fail(BISIP_EINVAL, "null argument");
     *n_plain = *n_comp = 0;
-    const int v = effective_variant(c);
-    if (c->model_id != BISIP_MODEL_POLYDECOMP) return BISIP_OK;
-    if (v == BISIP_VARIANT_REDUCED) *n_plain = c->E;
-    else if (v == BISIP_VARIANT_REDUCED_COMP) {
-        if (c->mixed)
-            for (unsigned char t : c->tier_of) ++*(t ? n_comp : n_plain);
-        else *n_comp = c->E;
+    for (size_t e = 0; e < (size_t)c->E; ++e) {
+        const int tier = running_tier(c, e);
+        if (tier >= 0) ++*(tier ? n_comp : n_plain);
     }
     return BISIP_OK;
 }
@@ -1157,8 +1144,7 @@ static double reduced_check_rows(const bisip_ctx *c, const double *theta, int64_
         reduced_logp_reference_rows(c->reduced[(size_t)spectrum], rows, held, want);
         for (int r = 0; r < held; ++r) {
             const double scale = std::fabs(want[r]) > 1.0 ? std::fabs(want[r]) : 1.0;
-            const double rel = std::fabs(got[r] - want[r]) / scale;
-            if (!(rel <= w)) w = rel;                          // NaN counts as worst
+            w = worse(w, std::fabs(got[r] - want[r]) / scale);
         }
         held = 0;
     };
@@ -1187,8 +1173,7 @@ int bisip_ctx_reduced_check(bisip_ctx *c, const double *theta, int64_t W, const 
             worst[(size_t)slot.fetch_add(1)] = reduced_check_rows(c, theta, W, logp, lo, hi, 1);
         });
         double all = 0.0;
-        for (double w : worst)
-            if (!(w <= all)) all = w;
+        for (double w : worst) all = worse(all, w);
         *worst_rel = all;
         return (int)BISIP_OK;
     });
@@ -1329,6 +1314,16 @@ static int guard_escalate(bisip_ctx *c, int v)
     return rc;
 }
 
+// One measurement of the tier that runs: counted and kept in the context's record first; then the answer to "must
+// the context leave this tier?" -- past GUARD_TOL (or NaN), and only a context that chose the tier itself.  Whether
+// the guard is switched on (guard_on) is asked by the callers, each where it always has.
+static bool guard_record(bisip_ctx *c, double worst)
+{
+    ++c->guard_checks;
+    c->guard_worst = worse(c->guard_worst, worst);
+    return !(worst <= GUARD_TOL) && c->variant == BISIP_VARIANT_AUTO;
+}
+
 // The QR-reduced kernels were chosen from an error ESTIMATE on probe rows (recenter_reduced); here the
 // kernel that just ran is MEASURED on up to 256 rows of the caller's own batch against the reduced form
 // in long double -- on the first call of a context and on every 2^n-th after it, so a long emcee run pays
@@ -1343,12 +1338,9 @@ static int guard_after_logprob(bisip_ctx *c, const double *theta, int64_t W, dou
     if (call & (call - 1)) return BISIP_OK;                       // 1, 2, 4, 8, ...
     for (int round = 0; round < 3; ++round) {
         const int v = effective_variant(c);
-        if (v != BISIP_VARIANT_REDUCED && v != BISIP_VARIANT_REDUCED_COMP) return BISIP_OK;
+        if (!is_reduced(v)) return BISIP_OK;
         const int64_t stride = W > 256 ? W / 256 : 1;
-        const double worst = reduced_check_rows(c, theta, W, logp, 0, W, stride);
-        ++c->guard_checks;
-        if (!(worst <= c->guard_worst)) c->guard_worst = worst;
-        if (worst <= GUARD_TOL || c->variant != BISIP_VARIANT_AUTO) return BISIP_OK;
+        if (!guard_record(c, reduced_check_rows(c, theta, W, logp, 0, W, stride))) return BISIP_OK;
         int rc = guard_escalate(c, v);
         if (rc != BISIP_OK) return rc;
         rc = logprob_host_once(c, theta, W, logp);
@@ -1370,14 +1362,12 @@ int bisip_ctx_reduced_guard_rows(bisip_ctx *c, const double *theta, int64_t W, c
         return fail(BISIP_EUNSUPPORTED, "only PolynomialDecomposition contexts have a QR-reduced form");
     if (W < 0 || (c->E > 1 && W % c->E)) return fail(BISIP_EINVAL, "W=%lld is not a multiple of the %d spectra", (long long)W, c->E);
     const int v = effective_variant(c);
-    if (v != BISIP_VARIANT_REDUCED && v != BISIP_VARIANT_REDUCED_COMP) return BISIP_OK;      // nothing estimated runs
+    if (!is_reduced(v)) return BISIP_OK;      // nothing estimated runs
     double worst = 0.0;
     int rc = bisip_ctx_reduced_check(c, theta, W, logp, &worst);
     if (rc != BISIP_OK) return rc;
-    ++c->guard_checks;
-    if (!(worst <= c->guard_worst)) c->guard_worst = worst;
     *worst_rel = worst;
-    if (worst <= GUARD_TOL || c->variant != BISIP_VARIANT_AUTO || !c->guard_on) return BISIP_OK;
+    if (!guard_record(c, worst) || !c->guard_on) return BISIP_OK;
     rc = guard_escalate(c, v);
     if (rc != BISIP_OK) return rc;
     *escalated = 1;

@@ -1,19 +1,87 @@
-// host.h -- what the translation units of libbisip_hip.so share: the context, the error
-// plumbing and the dispatch entry points.  The kernels are templates, so every dispatch_*.hip
+// host.h -- what the translation units of libbisip_hip.so share: the layout of the QR-reduced tiers'
+// operands, the context, the error plumbing and the dispatch entry points.  The kernels are templates, so every dispatch_*.hip
 // instantiates only its own family and the units compile in parallel.
 #pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstring>
+
+#include "../../include/bisip_hip.h"
+
+namespace bisip {
+namespace host {
+
+// One spectrum's operands for one QR-reduced tier (0 plain, 1 compensated) as the kernels hold them: an entry of
+// ReducedTier::image below, a kernel argument (fill_reduced), an element of the device array d_red -- all of them
+// ReducedArgs<P, COMP> of kernels.h, to which the static_asserts beside fill_reduced tie this description for every
+// degree.  In doubles, the compensated tier's low word of the triangle in front as floats, an even number of them
+// (the doubles that follow stay aligned; the padding float is 0).  pack and unpack are the only functions that
+// know the order of the fields.  Plain C++, no device: tests/native/sanitize_host.cpp runs them under the
+// sanitizers (BISIP_HOST_LAYOUT_ONLY: this part of the header alone).
+struct ReducedLayout {
+    int n;                  // unknowns, P + 2
+    size_t tri;             // entries of the packed upper triangle, row-major
+    size_t lo_floats;       // tri, made even
+
+    explicit constexpr ReducedLayout(int n_) : n(n_), tri((size_t)n_ * (n_ + 1) / 2), lo_floats((tri + 1) & ~(size_t)1) {}
+    constexpr size_t doubles(int tier) const { return (tier == 1 ? lo_floats / 2 : 0) + tri + 3 * (size_t)n + 1; }
+
+    // the triangle (and, tier 1, its low word) as full (n, n) matrices, the vectors, the scalar -> entry
+    void pack(int tier, double *entry, const double *Rfull, const float *Rlo_full, const double *bhat, const double *e,
+              const double *elo, double rest) const
+    {
+        if (tier == 1) {
+            std::memset(entry, 0, lo_floats * sizeof(float));
+            for (int i = 0, k = 0; i < n; ++i)
+                for (int j = i; j < n; ++j, ++k) std::memcpy((char *)entry + k * sizeof(float), &Rlo_full[(size_t)i * n + j], sizeof(float));
+            entry += lo_floats / 2;
+        }
+        for (int i = 0; i < n; ++i) entry = std::copy(Rfull + (size_t)i * n + i, Rfull + (size_t)i * n + n, entry);
+        for (const double *v : {bhat, e, elo}) entry = std::copy(v, v + n, entry);
+        *entry = rest;
+    }
+
+    // entry -> the packed triangle (and, tier 1, the tri floats of its low word), the vectors, the scalar
+    void unpack(int tier, const double *entry, double *R, float *Rlo, double *bhat, double *e, double *elo, double *rest) const
+    {
+        if (tier == 1) {
+            std::memcpy(Rlo, entry, tri * sizeof(float));
+            entry += lo_floats / 2;
+        }
+        std::copy(entry, entry + tri, R);
+        entry += tri;
+        for (double *v : {bhat, e, elo}) { std::copy(entry, entry + n, v); entry += n; }
+        *rest = *entry;
+    }
+
+    // a packed triangle (and its low word, if any) as the full (n, n) matrices the host emulation reads
+    // (host_emulate.inc: reduced_chi2_kernel); zero below the diagonal
+    void expand(const double *R, const float *Rlo, double *Rfull, float *Rlo_full) const
+    {
+        std::fill(Rfull, Rfull + (size_t)n * n, 0.0);
+        if (Rlo) std::fill(Rlo_full, Rlo_full + (size_t)n * n, 0.0f);
+        for (int i = 0, k = 0; i < n; ++i)
+            for (int j = i; j < n; ++j, ++k) {
+                Rfull[(size_t)i * n + j] = R[k];
+                if (Rlo) Rlo_full[(size_t)i * n + j] = Rlo[k];
+            }
+    }
+};
+
+}  // namespace host
+}  // namespace bisip
+
+#ifndef BISIP_HOST_LAYOUT_ONLY
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
-#include <cstring>
 #include <new>
 #include <type_traits>
 #include <vector>
 
-#include "../../include/bisip_hip.h"
 #include "errors.h"
 #include "host_precompute.h"
 #include "kernels.h"
@@ -64,14 +132,10 @@ struct bisip_ctx {
     // logprob_row_reduced<P, COMP>); each has its own expansion point, and the compensated tier its own
     // operands (triangle, rest) from the QR carried out in binary128 (host_precompute.h: ReducedProblem)
     struct ReducedTier {
-        std::vector<double> bhat, evec, elo;   // spectrum 0, for the kernarg segment
-        std::vector<double> Rpacked;            // spectrum 0, packed upper triangle as this tier's kernel holds it
-        std::vector<float> Rlo_packed;          // tier 1: its low word (even count)
-        double rest = 0.0;                      // spectrum 0
         double err = INFINITY;                  // worst estimated relative log-prob error over the spectra that RUN this tier; INFINITY: not estimated
         bool valid = false;                     // estimated for the current prior box (every spectrum that needs it)
-        void *d_red = nullptr;                  // (E,) ReducedArgs<P>: a batch's tiers; a lone spectrum's compensated tier from degree 6 on
-        std::vector<double> image;              // host copy of d_red (entries are rewritten spectrum by spectrum)
+        std::vector<double> image;              // (E,) entries of ReducedLayout, rewritten spectrum by spectrum: the one copy of the operands on the host
+        void *d_red = nullptr;                  // the image on the device, where a kernel reads it from memory (reduced_image_on_device)
         std::vector<double> est;                // the estimate of every spectrum (tier 1: 0 where the spectrum does not run it)
         std::vector<unsigned char> done;        // per spectrum: estimated for the current box
     };
@@ -125,17 +189,49 @@ namespace host {
 int effective_variant(const bisip_ctx *c);
 inline bool is_reduced(int v) { return v == BISIP_VARIANT_REDUCED || v == BISIP_VARIANT_REDUCED_COMP; }
 
-// kernarg image of spectrum 0's reduced operands for the tier a variant runs
+// Which QR-reduced tier spectrum e runs now: 0 plain, 1 compensated, -1 neither (another formulation runs)
+inline int running_tier(const bisip_ctx *c, size_t e)
+{
+    const int v = effective_variant(c);
+    if (v == BISIP_VARIANT_REDUCED_COMP) return c->mixed ? c->tier_of[e] : 1;
+    return v == BISIP_VARIANT_REDUCED ? 0 : -1;
+}
+
+// Does a tier's image go to the device (ReducedTier::d_red)?  Every tier of a batch; of a lone spectrum its
+// compensated tier from degree REDUCED_COMP_MEMORY_OPERANDS_FROM on, where the bulk launch reads the operands from
+// memory (dispatch_logprob.hip: launch_reduced).  For recenter_reduced, which uploads, and for build_context's
+// constant that travels with the image (d_lconst); everybody else asks d_red.
+inline bool reduced_image_on_device(const bisip_ctx *c, int tier)
+{
+    return c->E > 1 || (tier == 1 && c->P >= REDUCED_COMP_MEMORY_OPERANDS_FROM);
+}
+
+// ReducedLayout is the layout of ReducedArgs<P, COMP>, for every degree and both tiers
+template <int P, bool COMP>
+constexpr bool reduced_layout_is_the_kernels()
+{
+    using A = ReducedArgs<P, COMP>;
+    using Plain = ReducedArgs<P, false>;
+    constexpr ReducedLayout L(P + 2);
+    static_assert(std::is_trivially_copyable<A>::value && alignof(A) == alignof(double) &&
+                  sizeof(A) == sizeof(double) * L.doubles(COMP ? 1 : 0), "an entry is copied as bytes, doubles(tier) of them");
+    // the plain struct is standard-layout: its offsets; the compensated one is the low word's floats, then the plain one
+    static_assert(std::is_standard_layout<Plain>::value && offsetof(Plain, R) == 0 && offsetof(Plain, bhat) == 8 * L.tri &&
+                  offsetof(Plain, e) == 8 * (L.tri + L.n) && offsetof(Plain, elo) == 8 * (L.tri + 2 * L.n) &&
+                  offsetof(Plain, rest) == 8 * (L.tri + 3 * L.n), "order of the fields");
+    static_assert(!COMP || (sizeof(ReducedLow<P, true>) == sizeof(float) * L.lo_floats &&
+                            sizeof(A) == sizeof(ReducedLow<P, true>) + sizeof(Plain)), "the low word in front");
+    return true;
+}
+#define X(p) static_assert(reduced_layout_is_the_kernels<p, false>() && reduced_layout_is_the_kernels<p, true>(), "ReducedLayout");
+PD_CASES(X)
+#undef X
+
+// the kernel argument of a lone spectrum's launch: entry 0 of the image of the tier the kernel computes
 template <int P, bool COMP>
 inline void fill_reduced(const bisip_ctx *c, ReducedArgs<P, COMP> &r)
 {
-    const bisip_ctx::ReducedTier &t = c->red[COMP ? 1 : 0];
-    if constexpr (COMP) std::memcpy(r.Rlo, t.Rlo_packed.data(), sizeof(float) * t.Rlo_packed.size());
-    std::memcpy(r.R, t.Rpacked.data(), sizeof(r.R));
-    std::memcpy(r.bhat, t.bhat.data(), sizeof(r.bhat));
-    std::memcpy(r.e, t.evec.data(), sizeof(r.e));
-    std::memcpy(r.elo, t.elo.data(), sizeof(r.elo));
-    r.rest = t.rest;
+    std::memcpy(&r, c->red[COMP ? 1 : 0].image.data(), sizeof(r));
 }
 
 // A context's model shape as a template argument, for every host entry point that launches a model-templated kernel.
@@ -239,3 +335,4 @@ int dispatch_apply(const bisip_ctx *c, const StretchArgs &a, hipStream_t st);
 
 }  // namespace host
 }  // namespace bisip
+#endif  // BISIP_HOST_LAYOUT_ONLY

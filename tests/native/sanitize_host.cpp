@@ -11,6 +11,8 @@
 #include <string>
 #include <vector>
 
+#define BISIP_HOST_LAYOUT_ONLY          // host.h's device-free part: the layout of the QR-reduced tiers' operands
+#include "../../bisip_amd/csrc/host.h"
 #include "../../bisip_amd/csrc/host_precompute.h"
 #include "../../include/bisip_hip.h"
 
@@ -198,10 +200,62 @@ static void reduced(int N, int S, int D)
     }
 }
 
+// One spectrum's operands of a QR-reduced tier (host.h: ReducedLayout), pack -> unpack -> pack: every field comes
+// back bit for bit (a NaN and a -0.0 among them), the padding float of an odd triangle's low word is 0, nothing is
+// written past doubles(tier) -- the entries are heap blocks of exactly that size, and a buffer with sentinels
+// behind the entry says the same without a sanitizer.
+static void layout(int n)
+{
+    const bisip::host::ReducedLayout L(n);
+    const size_t tri = (size_t)n * (n + 1) / 2, nn = (size_t)n * n;
+    EXPECT(L.n == n && L.tri == tri && L.lo_floats % 2 == 0 && (L.lo_floats == tri || L.lo_floats == tri + 1));
+    const double SENTINEL = -7.5;
+    std::vector<double> Rf(nn, SENTINEL), bh(n), e(n), el(n);      // below the diagonal: never read
+    std::vector<float> Rlf(nn, (float)SENTINEL);
+    for (int i = 0; i < n; ++i) {
+        for (int j = i; j < n; ++j) { Rf[(size_t)i * n + j] = 1000.25 + i * n + j; Rlf[(size_t)i * n + j] = 1e-3f * (1 + i * n + j); }
+        bh[i] = 0.5 + i; e[i] = -1e-9 * (i + 1); el[i] = 1e-26 * (i + 1);
+    }
+    e[0] = -0.0; el[n - 1] = std::nan("");
+    const double rest = 123.456;
+    for (int tier = 0; tier < 2; ++tier) {
+        const size_t per = L.doubles(tier);
+        EXPECT(per == tri + 3 * (size_t)n + 1 + (tier ? L.lo_floats / 2 : 0));
+        std::vector<double> fenced(per + 4, SENTINEL), entry(per, SENTINEL), again(per, SENTINEL);
+        L.pack(tier, fenced.data(), Rf.data(), tier ? Rlf.data() : nullptr, bh.data(), e.data(), el.data(), rest);
+        for (size_t k = per; k < per + 4; ++k) EXPECT(fenced[k] == SENTINEL);
+        L.pack(tier, entry.data(), Rf.data(), tier ? Rlf.data() : nullptr, bh.data(), e.data(), el.data(), rest);
+        EXPECT(std::memcmp(entry.data(), fenced.data(), per * sizeof(double)) == 0);
+        std::vector<double> R(tri), bh2(n), e2(n), el2(n);
+        std::vector<float> Rlo(tri);
+        double rest2 = 0.0;
+        L.unpack(tier, entry.data(), R.data(), tier ? Rlo.data() : nullptr, bh2.data(), e2.data(), el2.data(), &rest2);
+        for (int i = 0, k = 0; i < n; ++i)
+            for (int j = i; j < n; ++j, ++k) {
+                EXPECT(std::memcmp(&R[k], &Rf[(size_t)i * n + j], sizeof(double)) == 0);
+                if (tier) EXPECT(std::memcmp(&Rlo[k], &Rlf[(size_t)i * n + j], sizeof(float)) == 0);
+            }
+        EXPECT(std::memcmp(bh2.data(), bh.data(), n * sizeof(double)) == 0 && std::memcmp(e2.data(), e.data(), n * sizeof(double)) == 0);
+        EXPECT(std::memcmp(el2.data(), el.data(), n * sizeof(double)) == 0 && std::memcmp(&rest2, &rest, sizeof(double)) == 0);
+        if (tier && L.lo_floats != tri) {                           // n = 2: tri = 3, one padding float
+            float pad = 1.0f;
+            std::memcpy(&pad, (const char *)entry.data() + tri * sizeof(float), sizeof(float));
+            EXPECT(pad == 0.0f && !std::signbit(pad));
+        }
+        std::vector<double> Rf2(nn, SENTINEL);
+        std::vector<float> Rlf2(nn, (float)SENTINEL);
+        L.expand(R.data(), tier ? Rlo.data() : nullptr, Rf2.data(), Rlf2.data());
+        for (int i = 1; i < n; ++i) for (int j = 0; j < i; ++j) EXPECT(Rf2[(size_t)i * n + j] == 0.0 && (!tier || Rlf2[(size_t)i * n + j] == 0.0f));
+        L.pack(tier, again.data(), Rf2.data(), tier ? Rlf2.data() : nullptr, bh2.data(), e2.data(), el2.data(), rest2);
+        EXPECT(std::memcmp(again.data(), entry.data(), per * sizeof(double)) == 0);
+    }
+}
+
 int main(int argc, char **argv)
 {
     if (argc > 1) ingest(argv[1]);
     blocks();
+    for (int n : {2, 7, 8, 12}) layout(n);          // degrees 0, 5, 6, 10
     for (int N : {2, 20}) for (int D : {1, 6, 11}) reduced(N, 2 * N, D);
     for (int N : {1, 2, 20, 33}) for (int S : {1, 7, 40}) for (int D : {1, 6, 11})
         for (double c : {1.0, 0.5}) operands(N, S, D, c);

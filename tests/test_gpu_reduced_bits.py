@@ -145,6 +145,27 @@ def test_bulk_routes(P, variant):
     ctx.close()
 
 
+def test_small_and_bulk_routes_are_held_to_the_same_operands():
+    """A lone spectrum at degree 6 on the compensated tier: 40 rows take the operands as a kernel argument, 2 x 256 x 256
+    rows read them from the device image.  Both are cut from one host image, which reduced_operands(0, 1) reads once:
+    both launches equal its emulation bit for bit, and the 40 rows, placed at the front of the big launch, give the
+    same bits in both."""
+    ctx, bounds, *_ = _pd_context(32, 6, 1.0, variant='reduced_comp')
+    ctx.reduced_guard(False)
+    assert ctx.kernel_name == KERNEL['reduced_comp']
+    ops = ctx.reduced_operands(0, 1)
+    assert ops['runs']
+    from bisip_amd import _hip
+    small = _box_rows(bounds, 40, 6)
+    big = np.vstack([small, _box_rows(bounds, 2 * 256 * 256 - 40, 7)])
+    got_small, got_big = ctx.logprob(small), ctx.logprob(big)
+    assert_same_bits(got_small, _hip.reduced_emulate(ops, bounds, small))
+    assert_same_bits(got_big, _hip.reduced_emulate(ops, bounds, big))
+    assert_same_bits(got_big[:40], got_small)
+    assert np.isfinite(got_small).sum() >= 30
+    ctx.close()
+
+
 @pytest.mark.parametrize('P,variant', [(6, 'reduced'), (8, 'reduced_comp')])
 def test_operands_follow_a_moved_box(P, variant):
     """bisip_ctx_set_bounds re-centres the reduced form: the kernel arguments of the small launches and the device image
