@@ -369,6 +369,7 @@ FILES = [
     (rn('sweep.jsonl, sweep_kernel_stats.csv'), '`python benchmarks/sweep.py` (and under `rocprofv3 --kernel-trace --stats`)', 'every log-probability kernel at the BASELINE config shapes'),
     (rn('host_path.jsonl'), '`python benchmarks/host_path.py`', 'PCIe-inclusive `bisip_logprob` rate; `bisip_forward_dev` store rate'),
     (rn('sampler_bench.jsonl, sampler_kernel_stats.csv'), '`python benchmarks/sampler_bench.py`', 'end-to-end `fit()` iterations/s per sampler / stream mode'),
+    ('moves_bench.jsonl', '`python benchmarks/moves_bench.py`', 'the differential-evolution and snooker moves beside the stretch move on the launch path: us per half-step (survey 512 x 256 double Cole-Cole; one ensemble of 4,096 single Cole-Cole) with the ratio to stretch, and the autocorrelation time of `log_tau_1` and the mode switch rate of the two-mode label-switching fit under stretch and under the 0.8 / 0.2 mixture'),
     (rn('cfg4_*.json'), '`python benchmarks/cfg4_sampler.py --steps 200 --chain device [--fused] [--loop rccl|rccl-own|python]`', 'BASELINE config 4 on one GPU: fused vs the sharded half-step driven from C over RCCL vs from Python'),
     (rn('cfg5_*.json, cfg5_kernel_stats.csv'), '`python benchmarks/cfg5_batch.py --chain device --steps 500 --thin-by 40 [--no-persistent]`', "BASELINE config 5, one GPU's share (512 spectra x 256 walkers)"),
     (rn('bench_2ranks_one_device*.json'), '`python bench.py --gpus 2 --backend gloo --same-device --full --walkers 1048576 --steps 4`', 'the self-launched 2-rank run on one GPU (gloo): result line and the sharded-sampler extra (state identical on both ranks = single-GPU chain)'),

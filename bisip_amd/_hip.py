@@ -40,6 +40,13 @@ class StretchArgs(ctypes.Structure):
                 ('walkers_per_spectrum', ctypes.c_int64)]
 
 
+class MoveArgs(ctypes.Structure):
+    """``bisip_move_args`` of include/bisip_hip.h."""
+    _fields_ = [('stretch', StretchArgs), ('active', ctypes.c_void_p), ('p0', ctypes.c_void_p), ('p1', ctypes.c_void_p),
+                ('p2', ctypes.c_void_p), ('gamma', ctypes.c_void_p), ('logu', ctypes.c_void_p),
+                ('snooker_gamma', ctypes.c_double)]
+
+
 class PersistArgs(ctypes.Structure):
     """``bisip_persist_args`` of include/bisip_hip.h."""
     _fields_ = [('coords', ctypes.c_void_p), ('logp', ctypes.c_void_p), ('n_walkers', ctypes.c_int64),
@@ -94,6 +101,12 @@ SYMBOLS = {
                                                     ctypes.c_int64, ctypes.c_double, ctypes.c_uint64, ctypes.c_int64,
                                                     ctypes.c_void_p, ctypes.c_void_p]),
     'bisip_stretch_persistent_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(PersistArgs), ctypes.c_void_p]),
+    'bisip_move_draw_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64,
+                                           ctypes.c_void_p, ctypes.c_double, ctypes.c_double] + [ctypes.c_void_p] * 7),
+    'bisip_move_half_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(MoveArgs), ctypes.c_int, ctypes.c_int64,
+                                           ctypes.c_void_p]),
+    'bisip_move_run_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(MoveArgs), ctypes.POINTER(ctypes.c_int32),
+                                          ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     'bisip_chain_moments_workspace': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
     'bisip_chain_moments_dev': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 4),
@@ -891,6 +904,27 @@ class HipContext:
                                                 int(n_steps), *[ctypes.c_void_p(p) for p in
                                                                 (perm, active, partner, zz, factor, logu)],
                                                 ctypes.c_void_p(stream)))
+
+    # -- differential-evolution and snooker moves (bisip_amd/moves.py) --------------------
+    def move_draw_dev(self, W, seed, step0, n_steps, perm, g0, sigma, active, p0, p1, p2, gamma, logu, stream=0):
+        """The moves' stream arrays (purposes 4, 5 and 1 of the Philox contract) for ``n_steps`` iterations; every
+        array argument is a device pointer."""
+        _check(self._lib.bisip_move_draw_dev(self._h, int(W), int(seed), int(step0), int(n_steps), ctypes.c_void_p(perm),
+                                             float(g0), float(sigma),
+                                             *[ctypes.c_void_p(p) for p in (active, p0, p1, p2, gamma, logu)],
+                                             ctypes.c_void_p(stream)))
+
+    def move_half_dev(self, args, kind, W, stream=0):
+        """One half-step of move ``kind`` (moves.MOVE_*) over a :class:`MoveArgs`; ``W``: walkers per ensemble."""
+        _check(self._lib.bisip_move_half_dev(self._h, ctypes.byref(args), int(kind), int(W), ctypes.c_void_p(stream)))
+
+    def move_run_dev(self, first_args, kinds, W, n_steps, thin_by=1, stream=0):
+        """``n_steps`` iterations back to back, iteration k running move ``kinds[k]`` (a host array of moves.MOVE_*)."""
+        kinds = np.ascontiguousarray(kinds, dtype=np.int32)
+        if kinds.shape != (int(n_steps),):
+            raise ValueError(f'kinds has shape {kinds.shape}, expected ({int(n_steps)},)')
+        _check(self._lib.bisip_move_run_dev(self._h, ctypes.byref(first_args), kinds.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                            int(W), int(n_steps), int(thin_by), ctypes.c_void_p(stream)))
 
 
 RCCL_ID_BYTES = 128

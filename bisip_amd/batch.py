@@ -130,8 +130,12 @@ class SpectraBatch(BatchCovariance, BatchIntervals, BatchEss, BatchDiagnostics, 
         Z = self.ctx.forward(theta.reshape(-1, self.ndim))
         return Z.reshape(theta.shape[0], theta.shape[1], 2, self.N)
 
-    def fit(self, p0=None, seed=None, thin_by=1, chain='host', persistent=None):
+    def fit(self, p0=None, seed=None, thin_by=1, chain='host', persistent=None, moves=None):
         """Run E independent stretch-move ensembles on the device (rng='philox').
+
+        ``moves``: 'stretch', 'de' or 'snooker', a ``bisip_amd.moves`` descriptor, a list of them or of ``(move, weight)``
+        (``[('de', 0.8), ('snooker', 0.2)]`` for spectra whose modes share a box): every ensemble runs the move drawn for
+        the iteration, one launch per half-step (``persistent`` None or False).
 
         ``thin_by``: store one sample every ``thin_by`` iterations (``nsteps`` samples are
         stored).  ``chain='device'`` keeps the stored samples in HBM: ``get_param_mean`` /
@@ -159,7 +163,7 @@ class SpectraBatch(BatchCovariance, BatchIntervals, BatchEss, BatchDiagnostics, 
         self.ctx.set_bounds(self.param_bounds)
         self._sampler = DeviceEnsembleSampler(Wp, ndim, self.ctx, rng='philox', seed=seed,
                                               n_ensembles=E, chain_on_device=(chain == 'device'),
-                                              persistent=persistent)
+                                              persistent=persistent, moves=moves)
         self._sampler.run_mcmc(np.asarray(p0).reshape(E * Wp, ndim), self.nsteps, thin_by=thin_by)
         # PolynomialDecomposition: the reduced kernels were chosen from an estimate; measure them on
         # the final ensembles against long double (see Inversion._check_reduced_kernel)

@@ -201,9 +201,12 @@ class Inversion(_plotlib, _utils.utils):
             pool: accepted for signature compatibility and ignored: the reference hands it to
                 emcee to spread the per-walker Python calls over processes
                 (src/bisip/models.py:91-94,115); here a whole half-ensemble is one kernel launch.
-            moves: an emcee ``moves`` object; requires emcee (the native samplers
-                implement the default StretchMove only) -- emcee then drives the vectorised
-                GPU log-probability (``vectorize=True``).
+            moves: 'stretch', 'de' or 'snooker', a ``bisip_amd.moves`` descriptor (``StretchMove``, ``DEMove``,
+                ``DESnookerMove``: emcee's names and arguments), a list of them or of ``(move, weight)`` -- e.g.
+                ``[('de', 0.8), ('snooker', 0.2)]``, emcee's advice for multimodal posteriors such as two Cole-Cole
+                modes in one box: the device sampler runs them itself (``rng='philox'``, which ``rng=None`` means
+                here; one launch per half-step).  Any other object is an emcee ``moves`` object and requires emcee,
+                which then drives the vectorised GPU log-probability (``vectorize=True``).
             sampler (str): 'device' (default) keeps the ensemble and the chain on the GPU
                 and runs one fused kernel per half-step; 'host' runs the stretch move in
                 NumPy around the vectorised GPU log-probability.  Same chain either way.
@@ -238,7 +241,21 @@ class Inversion(_plotlib, _utils.utils):
 
         ctx = self._context()
         ctx.set_bounds(self.param_bounds)  # bounds are read at fit() time, not at construction
-        if moves is not None:
+        from .moves import is_native
+        native = moves is not None and is_native(moves)
+        if native:
+            # 'stretch' | 'de' | 'snooker', their descriptors and weighted mixtures of them: the device sampler's own
+            # kernels, on the Philox stream
+            if sampler != 'device':
+                raise ValueError("native moves run in the device sampler only (sampler='device')")
+            if chain not in ('host', 'device'):
+                raise ValueError("chain must be 'host' or 'device'")
+            if rng not in (None, 'philox', 'auto'):
+                raise ValueError(f"native moves need rng='philox': their stream extends the Philox contract (got rng={rng!r})")
+            self._sampler = DeviceEnsembleSampler(self.nwalkers, self.ndim, ctx, rng='philox', persistent=persistent,
+                                                  chain_on_device=(chain == 'device'), moves=moves)
+            moves = None                    # (what follows treats the run as the device sampler's)
+        elif moves is not None:
             import emcee  # optional: non-default moves
             self._sampler = emcee.EnsembleSampler(self.nwalkers, self.ndim, ctx.logprob,
                                                   moves=moves, vectorize=True)

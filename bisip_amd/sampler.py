@@ -31,6 +31,10 @@ step, half, purpose)); only the per-step split -- an affine bijection (A, B) of 
 walker indices, ``affine_splits``, itself a pure function of (seed, step) -- is computed
 on the host.
 
+``moves=`` (DeviceEnsembleSampler, rng='philox', launch-per-half-step path, one rank) adds the differential-evolution
+and the snooker move and weighted mixtures of them with the stretch move: bisip_amd/moves.py states them and the
+purposes 3-5 their stream adds to the Philox contract; the stretch move's own numbers do not change.
+
 Sampler parity with emcee itself is UNPINNED (no emcee here, and the reference's
 tests assert nothing at this boundary); tests pin the two drivers against each other
 and against an oracle-driven replay.
@@ -775,6 +779,13 @@ class HipStretchBackend:
         next to the kernels of the previous chunk -- a persistent sampler kernel keeps one wave per
         SIMD busy and leaves the rest of the chip to it -- and the compute stream waits for it.
         ``after=None``: on the compute stream, as any other kernel."""
+        self._drawn(after, lambda stream: self.ctx.stretch_draw_dev(
+            W, a, seed, step0, n_steps, st['perm'].data_ptr(), st['active'].data_ptr(), st['partner'].data_ptr(),
+            st['zz'].data_ptr(), st['factor'].data_ptr(), st['logu'].data_ptr(), stream))
+
+    def _drawn(self, after, launch):
+        """``launch(stream)`` on the compute stream, or -- with ``after`` -- on the draw stream behind those events,
+        the compute stream then waiting for it."""
         stream = self.stream()
         if after is not None:
             torch = self.torch
@@ -784,14 +795,30 @@ class HipStretchBackend:
                 if ev is not None:
                     self._draw_stream.wait_event(ev)
             stream = self._draw_stream.cuda_stream
-        self.ctx.stretch_draw_dev(W, a, seed, step0, n_steps, st['perm'].data_ptr(),
-                                  st['active'].data_ptr(), st['partner'].data_ptr(),
-                                  st['zz'].data_ptr(), st['factor'].data_ptr(),
-                                  st['logu'].data_ptr(), stream)
+        launch(stream)
         if after is not None:
             done = self.torch.cuda.Event()
             done.record(self._draw_stream)
             self.torch.cuda.current_stream(self.device).wait_event(done)
+
+    def draw_moves(self, st, W, seed, step0, n_steps, g0, sigma, after=None):
+        """Fill a chunk's arrays of the differential-evolution and snooker moves (``bisip_move_draw_dev``: the st['mv_*']);
+        ``after`` as for ``draw``."""
+        self._drawn(after, lambda stream: self.ctx.move_draw_dev(
+            W, seed, step0, n_steps, st['perm'].data_ptr(), g0, sigma,
+            *[st['mv_' + name].data_ptr() for name in ('active', 'p0', 'p1', 'p2', 'gamma', 'logu')], stream))
+
+    def run_moves(self, st, n_steps, moves):
+        """All n_steps iterations of a chunk in one C call, iteration k running move st['kinds'][k]
+        (``bisip_move_run_dev``; 2 launches per step, no host round trip)."""
+        from ._hip import MoveArgs
+        W = st['coords'].shape[0]
+        m = MoveArgs()
+        m.stretch = self._args(st, 0, 0, (W + 1) // 2, base=True)
+        for name in ('active', 'p0', 'p1', 'p2', 'gamma', 'logu'):
+            setattr(m, name, st['mv_' + name].data_ptr())
+        m.snooker_gamma = moves['gammas']
+        self.ctx.move_run_dev(m, st['kinds'], W, n_steps, st.get('thin', 1), self.stream())
 
     def mark(self):
         """An event at the current end of the compute stream."""
@@ -829,9 +856,38 @@ class DeviceEnsembleSampler(DeviceChainSummaries, _SamplerBase):
     def __init__(self, nwalkers, ndim, ctx=None, a=2.0, live_dangerously=False, group=None,
                  distributed=False, backend=None, chunk=None, rng='numpy', seed=None,
                  n_ensembles=1, force_sharded_path=False, persistent=None, chain_on_device=False,
-                 sharded_loop='python'):
+                 sharded_loop='python', moves=None):
         if rng not in ('numpy', 'philox'):
             raise ValueError("rng must be 'numpy' or 'philox'")
+        # moves: None (the stretch move, every path and stream above), or native moves as bisip_amd.moves.parse_moves
+        # takes them -- 'stretch' | 'de' | 'snooker', their descriptors, a list of them or of (move, weight).  They run
+        # on the launch-per-half-step path with rng='philox' on one rank; iteration k runs the move that
+        # moves.move_schedule draws for it, a stretch iteration exactly what it would run under moves=None.
+        self._moves = None
+        if moves is not None:
+            from . import moves as mv
+            mlist, weights = mv.parse_moves(moves)
+            if rng != 'philox':
+                raise ValueError("native moves need rng='philox': their stream extends the Philox contract "
+                                 f"(got rng={rng!r})")
+            if distributed or force_sharded_path or (isinstance(sharded_loop, str) and sharded_loop.startswith('simulate:')):
+                raise ValueError('native moves run on one rank: the sharded half-step has no move kernels')
+            if persistent:
+                raise ValueError('native moves run on the launch-per-half-step path: the persistent kernels '
+                                 'implement the stretch move only (persistent=None or False)')
+            persistent = False
+            by_kind = {m.kind: m for m in mlist}
+            if mv.MOVE_DE in by_kind and int(nwalkers) // 2 < 2:
+                raise ValueError(f"the 'de' move needs two partners in the other half: {nwalkers} walkers, at least 4")
+            if mv.MOVE_SNOOKER in by_kind and int(nwalkers) // 2 < 3:
+                raise ValueError(f"the 'snooker' move needs three partners in the other half: {nwalkers} walkers, at least 6")
+            if backend is not None and not (hasattr(backend, 'draw_moves') and hasattr(backend, 'run_moves')):
+                raise ValueError('this backend has no hooks for native moves (draw_moves, run_moves)')
+            if mv.MOVE_STRETCH in by_kind:
+                a = by_kind[mv.MOVE_STRETCH].a          # a StretchMove in the list states the scale itself
+            de, snooker = by_kind.get(mv.MOVE_DE, mv.DEMove()), by_kind.get(mv.MOVE_SNOOKER, mv.DESnookerMove())
+            self._moves = dict(moves=mlist, weights=weights, stretch=mv.MOVE_STRETCH in by_kind, kinds=np.array([m.kind for m in mlist], dtype=np.int32),
+                               g0=float(de.g0(int(ndim))), sigma=de.sigma, gammas=snooker.gammas)
         # n_ensembles > 1: independent ensembles of `nwalkers` walkers each (batch of spectra),
         # stacked as rows [e*nwalkers, (e+1)*nwalkers); the chain is (nsteps, E*nwalkers, ndim)
         self.n_ensembles = int(n_ensembles)
@@ -1019,7 +1075,9 @@ class DeviceEnsembleSampler(DeviceChainSummaries, _SamplerBase):
         # launches draw the stream themselves).  2 GiB
         # per chunk is <1 % of the 288 GB of HBM and keeps the host work per chunk negligible
         # (the Philox stream is double-buffered: the next chunk's is drawn while this one runs)
-        per_step = self.nwalkers * (8 * self.ndim + 8 + (0 if stream_in_place else 2 if self.rng == 'philox' else 1) * (3 * 8 + 2 * 4))
+        stretch_arrays = not stream_in_place and (self._moves is None or self._moves['stretch'])
+        per_step = self.nwalkers * (8 * self.ndim + 8 + (0 if not stretch_arrays else 2 if self.rng == 'philox' else 1) * (3 * 8 + 2 * 4)
+                                    + (2 * (2 * 8 + 4 * 4) if self._moves is not None else 0))
         n = max(1, min(nsteps, (2 << 30) // per_step))
         if self.rng == 'numpy':
             # the NumPy-order stream is drawn on the host (MT19937 is sequential: ~20-60 ns per
@@ -1092,7 +1150,10 @@ class DeviceEnsembleSampler(DeviceChainSummaries, _SamplerBase):
         be = self.backend
         W, ndim = self.nwalkers, self.ndim
         single = self._world == 1 and not self.force_sharded_path
-        if single and self.persistent and 'inline' not in st and be.run_persistent(st, self.walkers_per_ensemble, n):
+        if self._moves is not None:
+            be.run_moves(st, n, self._moves)
+            self.last_path = 'launch-per-half-step'
+        elif single and self.persistent and 'inline' not in st and be.run_persistent(st, self.walkers_per_ensemble, n):
             # one workgroup per ensemble, or -- a single ensemble beyond that -- several with a barrier of their own
             self.last_path = 'persistent' if self.walkers_per_ensemble * (ndim + 1) * 8 <= 65536 and (self.walkers_per_ensemble + 1) // 2 <= 512 \
                 else 'persistent-multi-workgroup'
@@ -1160,7 +1221,7 @@ class DeviceEnsembleSampler(DeviceChainSummaries, _SamplerBase):
         # A single ensemble big enough for the packed-state half-step has its Philox stream drawn by the half-step
         # launches themselves: no stream arrays (34 MB per iteration at a million walkers), no draw kernel.
         in_place = (self.rng == 'philox' and self.n_ensembles == 1 and self._world == 1 and not self.force_sharded_path
-                    and not self.simulate_world and hasattr(be, 'draws_in_place') and be.draws_in_place(W))
+                    and not self.simulate_world and self._moves is None and hasattr(be, 'draws_in_place') and be.draws_in_place(W))
         self.last_stream = 'in place' if in_place else ('arrays' if self.rng == 'philox' else 'host')
         # stored samples per chunk, known up front so that the next chunk's stream can be drawn ahead
         sizes, left = [], nsteps
@@ -1244,20 +1305,32 @@ class DeviceEnsembleSampler(DeviceChainSummaries, _SamplerBase):
                 st['inline'] = (self.a, self.seed, it0)
             elif self.rng == 'philox':
                 b = k % 2
+                kinds_of = ()
+                if self._moves is None or self._moves['stretch']:     # (moves without a StretchMove never read them)
+                    kinds_of += (('active', torch.int32), ('partner', torch.int32), ('zz', torch.float64),
+                                 ('factor', torch.float64), ('logu', torch.float64))
+                if self._moves is not None:      # the moves' arrays (bisip_move_draw_dev) beside the stretch move's
+                    kinds_of += (('mv_active', torch.int32), ('mv_p0', torch.int32), ('mv_p1', torch.int32),
+                                 ('mv_p2', torch.int32), ('mv_gamma', torch.float64), ('mv_logu', torch.float64))
                 if stream_bufs[0] is None:       # chunks never grow: later ones reuse these two sets
                     for i, rows in enumerate([sizes[0] * thin_by] + ([sizes[1] * thin_by] if len(sizes) > 1 else [])):
-                        stream_bufs[i] = {name: be.empty((rows, 2, nh), dt) for name, dt in (
-                            ('active', torch.int32), ('partner', torch.int32), ('zz', torch.float64),
-                            ('factor', torch.float64), ('logu', torch.float64))}
+                        stream_bufs[i] = {name: be.empty((rows, 2, nh), dt) for name, dt in kinds_of}
                     if perm_ev is not None:      # the side stream starts after the split upload AND these
                         perm_ev = be.mark()      # allocations (the allocator may hand out memory still in use upstream)
                 for name, buf in stream_bufs[b].items():
                     st[name] = buf[:n]
-                if len(sizes) > 1 and perm_ev is not None:
-                    # beside the previous chunk's kernels; this set was last read two chunks ago
-                    be.draw(st, self.walkers_per_ensemble, self.a, self.seed, it0, n, after=(perm_ev, free_ev[b]))
-                else:
-                    be.draw(st, self.walkers_per_ensemble, self.a, self.seed, it0, n)
+                # beside the previous chunk's kernels; this set was last read two chunks ago
+                beside = dict(after=(perm_ev, free_ev[b])) if len(sizes) > 1 and perm_ev is not None else {}
+                stretch_runs = True
+                if self._moves is not None:
+                    from .moves import MOVE_STRETCH, move_schedule
+                    # the move of every iteration of the chunk: a pure function of (seed, step), like the splits
+                    mv = self._moves
+                    st['kinds'] = mv['kinds'][move_schedule(self.seed, it0, n, mv['weights'])]
+                    stretch_runs = bool((st['kinds'] == MOVE_STRETCH).any())
+                    be.draw_moves(st, self.walkers_per_ensemble, self.seed, it0, n, mv['g0'], mv['sigma'], **beside)
+                if stretch_runs:
+                    be.draw(st, self.walkers_per_ensemble, self.a, self.seed, it0, n, **beside)
             fresh = bool(self._dev.pop('fresh', False)) and k == 0
             saved_ev = None
             if guard is not None:
@@ -1275,7 +1348,9 @@ class DeviceEnsembleSampler(DeviceChainSummaries, _SamplerBase):
                     if in_place:
                         sub['perm'] = st['perm'][lo * thin_by:hi * thin_by]
                         sub['inline'] = (self.a, self.seed, it0 + lo * thin_by)
-                    for name in ('active', 'partner', 'zz', 'factor', 'logu') if not in_place else ():
+                    for name in [name for name in ('active', 'partner', 'zz', 'factor', 'logu') if name in st]:
+                        sub[name] = st[name][lo * thin_by:hi * thin_by]
+                    for name in [name for name in st if name == 'kinds' or name.startswith('mv_')]:
                         sub[name] = st[name][lo * thin_by:hi * thin_by]
                     sub['chain'], sub['logp_chain'] = st['chain'][lo:hi], st['logp_chain'][lo:hi]
                     return sub

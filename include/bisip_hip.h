@@ -313,6 +313,65 @@ typedef struct bisip_persist_args {
 } bisip_persist_args;
 int bisip_stretch_persistent_dev(bisip_ctx *ctx, const bisip_persist_args *args, void *stream);
 
+/* ---- differential-evolution and snooker moves beside the stretch move (emcee's DEMove and DESnookerMove, the
+ * mixture emcee advises for multimodal targets; the reference hands `moves` to emcee: src/bisip/models.py:84,111-118).
+ * Launch-per-half-step path, rng = Philox, one rank; single-spectrum and batch contexts.  The red/blue halves and the
+ * active walker of slot t are the stretch contract's; partners are members of the complementary half (Nc members),
+ * addressed by rank r -> walker pi^-1(2r + 1 - h).
+ *   DE (ter Braak 2006):  q_k = s_k + gamma (ca_k - cb_k), gamma = g0 (1 + sigma n), n ~ N(0,1); factor = 0
+ *   snooker (ter Braak & Vrugt 2008):  d = s - z, n2 = sum d_k^2, u = d / sqrt(n2), p1 = sum u_k z1_k,
+ *        p2 = sum u_k z2_k, q_k = s_k + u_k (gammas (p1 - p2)), m2 = sum (q_k - z_k)^2,
+ *        factor = 0.5 (ndim - 1) (ln m2 - ln n2); n2 == 0 is a rejection that raises no flag
+ *   (sums over k = 0 .. ndim-1, multiply then add, nothing contracted)
+ *   accept iff (factor + logp(q)) - logp(s) > logu; a NaN log-probability sets status bit 0, -inf rejects.
+ * emcee 3's snooker divides by sqrt(norm) and takes the logs of the norms, not of their squares: that is not the
+ * published move and is not what runs here.  bisip_amd/moves.py states moves and stream in NumPy.
+ *
+ * The stream extends the Philox contract (bisip_amd/csrc/sampler_kernels.h, DrawArgs): same key, the counter's
+ * fourth word names the purpose, purposes 0-2 keep every number they give.
+ *   3, counter (k, 0, 0, 3):        the iteration's move among weighted moves (host: moves.py, move_schedule)
+ *   4, counter (t, k, h | e<<1, 4): i0 = (x0 Nc) >> 32; i1 = (x1 (Nc-1)) >> 32, +1 if >= i0;
+ *                                   i2 = (x2 (Nc-2)) >> 32, +1 if >= min(i0,i1), then +1 if >= max(i0,i1)
+ *                                   DE: a, b = i0, i1;  snooker: z, z1, z2 = i0, i1, i2
+ *   5, counter (t, k, h | e<<1, 5): n = sqrt(-2 ln(1 - u53(x0,x1))) cos(2 pi u53(x2,x3))
+ *   logu: the purpose-1 number of the slot.
+ *
+ * bisip_move_args: `stretch` holds the state, the chain rows and the counters of bisip_stretch_args, and -- for the
+ * stretch iterations of a mixture -- the arrays bisip_stretch_draw_dev wrote; the other fields are the arrays of
+ * bisip_move_draw_dev, laid out alike ((n_steps, 2, E, nh), global walker ids; p2 is 0 where Nc < 3). */
+#define BISIP_MOVE_STRETCH 0
+#define BISIP_MOVE_DE 1
+#define BISIP_MOVE_SNOOKER 2
+typedef struct bisip_move_args {
+    bisip_stretch_args stretch;
+    const int32_t *active;
+    const int32_t *p0;
+    const int32_t *p1;
+    const int32_t *p2;
+    const double *gamma;   /* DE: g0 (1 + sigma n) */
+    const double *logu;
+    double snooker_gamma;  /* snooker: gammas */
+} bisip_move_args;
+
+/* Fill the arrays of purposes 4, 5 and 1 for n_steps iterations (arguments as for bisip_stretch_draw_dev).
+ * BISIP_EINVAL for W < 4 (a half of fewer than two members has no pair). */
+int bisip_move_draw_dev(bisip_ctx *ctx, int64_t W, uint64_t seed, int64_t step0, int64_t n_steps,
+                        const int32_t *d_perm, double de_g0, double de_sigma, int32_t *d_active, int32_t *d_p0,
+                        int32_t *d_p1, int32_t *d_p2, double *d_gamma, double *d_logu, void *stream);
+
+/* One half-step of move `kind` (BISIP_MOVE_*; BISIP_MOVE_STRETCH is bisip_stretch_half_dev on args->stretch).
+ * W = walkers per ensemble.  BISIP_EINVAL when the complementary half has fewer than 2 members (DE: W >= 4) or 3
+ * (snooker: W >= 6); BISIP_EUNSUPPORTED for the faithful / wave formulation, as the stretch dispatch says. */
+int bisip_move_half_dev(bisip_ctx *ctx, const bisip_move_args *args, int kind, int64_t W, void *stream);
+
+/* n_steps whole iterations back to back on `stream`: iteration k runs move kinds[k] (a HOST array of BISIP_MOVE_*,
+ * read before the call returns).  `first`, W, thin_by as for bisip_stretch_run_dev; every array advances by nh per
+ * half-step.  A run whose kinds are all BISIP_MOVE_STRETCH is bisip_stretch_run_dev's chain bit for bit -- but not
+ * its speed for one ensemble of 131,072 walkers or more: the state stays in its plain layout here, so a stretch
+ * iteration runs the plain half-step, never the packed-state one, and the stream always comes from its arrays. */
+int bisip_move_run_dev(bisip_ctx *ctx, const bisip_move_args *first, const int32_t *kinds, int64_t W,
+                       int64_t n_steps, int64_t thin_by, void *stream);
+
 /* Posterior mean and (population) standard deviation of every parameter, per ensemble, of a
  * chain resident in device memory -- the device form of get_param_mean / get_param_std
  * (src/bisip/utils.py:55-85: np.mean / np.std over the flattened chain) for batches whose
