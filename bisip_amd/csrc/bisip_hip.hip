@@ -1043,7 +1043,7 @@ struct PhiloxStream {
 static int stretch_run(bisip_ctx *c, const bisip_stretch_args *first, int64_t W, int64_t n_steps, int64_t thin_by,
                        const PhiloxStream *draw, void *stream)
 {
-    const int64_t nh = (W + 1) / 2;
+    const ChunkWalk walk(W, c->ndim, n_steps, thin_by, first->chain_row, first->logp_row);
     bisip_stretch_args u = *first;
     // A single ensemble that fills the chip with one lane per slot samples this chunk on a packed state: one aligned
     // 64-byte row per walker (k_stretch_half_packed), packed here, unpacked after the last half-step.
@@ -1063,16 +1063,13 @@ static int stretch_run(bisip_ctx *c, const bisip_stretch_args *first, int64_t W,
     }
     for (int64_t k = 0; k < n_steps; ++k) {
         for (int h = 0; h < 2; ++h) {
-            const int64_t off = (k * 2 + h) * nh;
+            const ChunkWalk::Half half = walk.at(k, h);
             if (!draw) {
+                const int64_t off = half.off;
                 u.active = first->active + off; u.partner = first->partner + off;
                 u.zz = first->zz + off; u.factor = first->factor + off; u.logu = first->logu + off;
             }
-            u.n_slots = h ? W / 2 : nh;
-            const bool store = ((k + 1) % thin_by) == 0;   // the walkers of BOTH halves of a stored step
-            const int64_t srow = k / thin_by;
-            u.chain_row = (store && first->chain_row) ? first->chain_row + srow * W * c->ndim : nullptr;
-            u.logp_row = (store && first->logp_row) ? first->logp_row + srow * W : nullptr;
+            u.n_slots = half.n_slots; u.chain_row = half.chain_row; u.logp_row = half.logp_row;
             StretchArgs a = to_device_args(&u);
             if (packed) a.packed = c->d_packed;
             if (draw) {
@@ -1097,8 +1094,7 @@ int bisip_stretch_run_dev(bisip_ctx *c, const bisip_stretch_args *first, int64_t
                           int64_t thin_by, void *stream)
 {
     if (!c || !first) return fail(BISIP_EINVAL, "null argument");
-    if (thin_by < 1 || n_steps % thin_by) return fail(BISIP_EINVAL, "n_steps=%lld must be a multiple of thin_by=%lld", (long long)n_steps, (long long)thin_by);
-    if (W < 2 || n_steps < 0) return fail(BISIP_EINVAL, "bad W=%lld or n_steps=%lld", (long long)W, (long long)n_steps);
+    if (const int rc = check_chunk(W, n_steps, thin_by)) return rc;
     if (!first->coords || !first->logp || !first->active || !first->partner || !first->zz ||
         !first->factor || !first->logu || !first->status)
         return fail(BISIP_EINVAL, "null buffer");
@@ -1116,7 +1112,7 @@ int bisip_stretch_run_philox_dev(bisip_ctx *c, const bisip_stretch_args *first, 
                                  void *stream)
 {
     if (!c || !first || !d_perm) return fail(BISIP_EINVAL, "null argument");
-    if (thin_by < 1 || n_steps % thin_by) return fail(BISIP_EINVAL, "n_steps=%lld must be a multiple of thin_by=%lld", (long long)n_steps, (long long)thin_by);
+    if (const int rc = check_chunk(W, n_steps, thin_by, true)) return rc;
     if (W < 2 || W > 0x7fffffffLL || n_steps < 0 || step0 < 0 || step0 + n_steps > 0xffffffffLL)
         return fail(BISIP_EINVAL, "bad W=%lld or step range [%lld, +%lld)", (long long)W, (long long)step0, (long long)n_steps);
     if (!(a > 0.0)) return fail(BISIP_EINVAL, "stretch scale a=%g must be positive", a);
@@ -1218,29 +1214,13 @@ int bisip_stretch_draw_dev(bisip_ctx *c, int64_t W, double a, uint64_t seed, int
         return fail(BISIP_EINVAL, "bad W/step range");
     if (n_steps == 0) return BISIP_OK;
     HIP_TRY(hipSetDevice(c->device));
-    DrawArgs d;
-    d.W = W; d.nh = (W + 1) / 2; d.n_steps = n_steps; d.step0 = step0; d.E = c->E; d.e0 = c->spectrum_offset;
     if (c->E > 1 && (W & 1)) return fail(BISIP_EINVAL, "batch context: walkers per spectrum must be even");
+    DrawArgs d;
+    d.s = draw_head(c, W, seed, step0, n_steps, d_perm);
     d.a = a; d.ndim_m1 = (double)(c->ndim - 1);
-    d.seed_lo = (unsigned int)(seed & 0xffffffffu); d.seed_hi = (unsigned int)(seed >> 32);
-    d.perm = d_perm; d.active = d_active; d.partner = d_partner;
+    d.active = d_active; d.partner = d_partner;
     d.zz = d_zz; d.factor = d_factor; d.logu = d_logu;
-    const long long per_half = d.E * d.nh, halves = 2 * n_steps;
-    d.flat = per_half < 256 && per_half * halves + 256 <= 0xffffffffLL;
-    if (d.flat) {
-        hipLaunchKernelGGL(k_stretch_draw, dim3((unsigned)((per_half * halves + 255) / 256)), dim3(256), 0,
-                           (hipStream_t)stream, d);
-        HIP_TRY(hipGetLastError());
-        return BISIP_OK;
-    }
-    if ((per_half + 255) / 256 > 0x7fffffffLL) return fail(BISIP_EINVAL, "too many slots per half-step");
-    const unsigned gy = (unsigned)(halves < 32768 ? halves : 32768);
-    const long long gz = (halves + gy - 1) / gy;
-    if (gz > 65535) return fail(BISIP_EINVAL, "n_steps=%lld too large for one draw (chunk the run)", (long long)n_steps);
-    hipLaunchKernelGGL(k_stretch_draw, dim3((unsigned)((per_half + 255) / 256), gy, (unsigned)gz), dim3(256), 0,
-                       (hipStream_t)stream, d);
-    HIP_TRY(hipGetLastError());
-    return BISIP_OK;
+    return launch_draw(d.s.E * d.s.nh, 2 * n_steps, k_stretch_draw, d, (hipStream_t)stream);
 }
 
 int bisip_stretch_persistent_dev(bisip_ctx *c, const bisip_persist_args *u, void *stream)

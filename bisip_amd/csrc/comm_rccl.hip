@@ -130,14 +130,14 @@ static int run_sharded(bisip_ctx *c, void *comm, int world, int rank, const bisi
                        int64_t n_steps, int64_t thin_by, void *stream)
 {
     if (c->E > 1) return fail(BISIP_EUNSUPPORTED, "a batch of spectra shards as whole replicas: no sharded half-step");
-    if (thin_by < 1 || n_steps % thin_by) return fail(BISIP_EINVAL, "n_steps=%lld must be a multiple of thin_by=%lld", (long long)n_steps, (long long)thin_by);
-    if (W < 2 || n_steps < 0) return fail(BISIP_EINVAL, "bad W=%lld or n_steps=%lld", (long long)W, (long long)n_steps);
+    if (const int rc = check_chunk(W, n_steps, thin_by)) return rc;
     if (!first->coords || !first->logp || !first->active || !first->partner || !first->zz ||
         !first->factor || !first->logu || !first->status)
         return fail(BISIP_EINVAL, "null buffer");
     if (world < 1 || rank < 0 || rank >= world) return fail(BISIP_EINVAL, "bad world=%d rank=%d", world, rank);
     HIP_TRY(hipSetDevice(c->device));
-    const int64_t nh = (W + 1) / 2;
+    const ChunkWalk walk(W, c->ndim, n_steps, thin_by, first->chain_row, first->logp_row);
+    const int64_t nh = walk.nh;
     const int64_t row = c->ndim + 2;                     // position, log-prob, accepted
     const int64_t pad_max = (nh + world - 1) / world;    // rows per rank slab (half 0 is the larger)
     const size_t need = (size_t)world * pad_max * row * sizeof(double);
@@ -152,15 +152,11 @@ static int run_sharded(bisip_ctx *c, void *comm, int world, int rank, const bisi
     int rc = BISIP_OK;
     for (int64_t k = 0; k < n_steps; ++k) {
         for (int h = 0; h < 2; ++h) {
-            const int64_t off = (k * 2 + h) * nh;
+            const ChunkWalk::Half half = walk.at(k, h);
+            const int64_t off = half.off, m = half.n_slots;
             u.active = first->active + off; u.partner = first->partner + off;
             u.zz = first->zz + off; u.factor = first->factor + off; u.logu = first->logu + off;
-            const int64_t m = h ? W / 2 : nh;
-            u.n_slots = m;
-            const bool store = ((k + 1) % thin_by) == 0;
-            const int64_t srow = k / thin_by;
-            u.chain_row = (store && first->chain_row) ? first->chain_row + srow * W * c->ndim : nullptr;
-            u.logp_row = (store && first->logp_row) ? first->logp_row + srow * W : nullptr;
+            u.n_slots = m; u.chain_row = half.chain_row; u.logp_row = half.logp_row;
             // a rank's block of the active half (dist.py:shard_range): the first m % world ranks
             // own one slot more
             const int64_t base = m / world, extra = m % world;

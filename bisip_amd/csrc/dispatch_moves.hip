@@ -1,36 +1,12 @@
 // dispatch_moves.hip -- differential-evolution and snooker half-steps, single spectrum, and the entry points of
-// the moves (draw / half / run); the batch-of-spectra instantiations live in dispatch_moves_batch.hip.
+// the moves (draw / half / run); the batch-of-spectra instantiations live in dispatch_moves_batch.hip.  The functor a
+// launch takes comes from lp_build.h.
 #include "move_launch.h"
 
 using namespace bisip;
 using namespace bisip::host;
 
 namespace {
-
-template <class M>
-int move_generic(const bisip_ctx *c, const MoveArgs &a, int kind, hipStream_t st)
-{
-    const ModelOperands o{c->d_cb_lp ? c->d_cb_lp : c->d_cb, c->N, c->lconst};
-    if constexpr (CoopLimit<M>::value > 0) {      // (else one lane per slot: the other kernels are never instantiated)
-        switch (move_lanes(a)) {
-        case 4: { GenericLP<M, 4> lp; lp.o = o; lp.b = c->bounds; return launch_move(a, kind, lp, st); }
-        case 2: { GenericLP<M, 2> lp; lp.o = o; lp.b = c->bounds; return launch_move(a, kind, lp, st); }
-        default: break;
-        }
-    }
-    GenericLP<M, 1> lp; lp.o = o; lp.b = c->bounds;
-    return launch_move(a, kind, lp, st);
-}
-
-template <int P, bool COMP>
-int move_reduced(const bisip_ctx *c, const MoveArgs &a, int kind, hipStream_t st)
-{
-    ReducedLP<P, COMP> lp;
-    fill_reduced<P, COMP>(c, lp.r);
-    lp.lconst = c->lconst;
-    lp.b = c->bounds;
-    return launch_move(a, kind, lp, st);
-}
 
 MoveArgs to_move_args(const bisip_move_args *u)
 {
@@ -75,15 +51,10 @@ int dispatch_move(const bisip_ctx *c, const MoveArgs &a, int kind, long long Wp,
         if (Wp < 2 || (Wp & 1)) return fail(BISIP_EINVAL, "batch context: walkers_per_spectrum must be even and >= 2, got %lld", Wp);
         return dispatch_move_batch(c, a, kind, Wp, st);
     }
-    if (c->model_id == BISIP_MODEL_POLYDECOMP) {
-        const int v = effective_variant(c);
-        if (v == BISIP_VARIANT_FAITHFUL || v == BISIP_VARIANT_WAVE)
-            return fail(BISIP_EUNSUPPORTED, "the device moves have no kernel for the faithful / wave "
-                        "formulation: use variant auto, reduced or collapsed");
-        if (v == BISIP_VARIANT_REDUCED) return with_pd_degree(c, "move", [&](auto p) { return move_reduced<p, false>(c, a, kind, st); });
-        if (v == BISIP_VARIANT_REDUCED_COMP) return with_pd_degree(c, "move", [&](auto p) { return move_reduced<p, true>(c, a, kind, st); });
-    }
-    return with_model(c, "move", [&](auto m) { return move_generic<typename decltype(m)::type>(c, a, kind, st); });
+    return with_lone_lp<4>(c, move_lanes(a), "move",
+                           "the device moves have no kernel for the faithful / wave "
+                           "formulation: use variant auto, reduced or collapsed",
+                           [&](const auto &lp) { return launch_move(a, kind, lp, st); });
 }
 
 }  // namespace host
@@ -103,25 +74,10 @@ int bisip_move_draw_dev(bisip_ctx *c, int64_t W, uint64_t seed, int64_t step0, i
     if (n_steps == 0) return BISIP_OK;
     HIP_TRY(hipSetDevice(c->device));
     MoveDrawArgs d;
-    d.W = W; d.nh = (W + 1) / 2; d.n_steps = n_steps; d.step0 = step0; d.E = c->E; d.e0 = c->spectrum_offset;
+    d.s = draw_head(c, W, seed, step0, n_steps, d_perm);
     d.g0 = de_g0; d.sigma = de_sigma;
-    d.seed_lo = (unsigned int)(seed & 0xffffffffu); d.seed_hi = (unsigned int)(seed >> 32);
-    d.perm = d_perm; d.active = d_active; d.p0 = d_p0; d.p1 = d_p1; d.p2 = d_p2; d.gamma = d_gamma; d.logu = d_logu;
-    // the two launch shapes of bisip_stretch_draw_dev
-    const long long per_half = d.E * d.nh, halves = 2 * n_steps;
-    d.flat = per_half < 256 && per_half * halves + 256 <= 0xffffffffLL;
-    if (d.flat) {
-        hipLaunchKernelGGL(k_move_draw, dim3((unsigned)((per_half * halves + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d);
-        HIP_TRY(hipGetLastError());
-        return BISIP_OK;
-    }
-    if ((per_half + 255) / 256 > 0x7fffffffLL) return fail(BISIP_EINVAL, "too many slots per half-step");
-    const unsigned gy = (unsigned)(halves < 32768 ? halves : 32768);
-    const long long gz = (halves + gy - 1) / gy;
-    if (gz > 65535) return fail(BISIP_EINVAL, "n_steps=%lld too large for one draw (chunk the run)", (long long)n_steps);
-    hipLaunchKernelGGL(k_move_draw, dim3((unsigned)((per_half + 255) / 256), gy, (unsigned)gz), dim3(256), 0, (hipStream_t)stream, d);
-    HIP_TRY(hipGetLastError());
-    return BISIP_OK;
+    d.active = d_active; d.p0 = d_p0; d.p1 = d_p1; d.p2 = d_p2; d.gamma = d_gamma; d.logu = d_logu;
+    return launch_draw(d.s.E * d.s.nh, 2 * n_steps, k_move_draw, d, (hipStream_t)stream);
 }
 
 int bisip_move_half_dev(bisip_ctx *c, const bisip_move_args *u, int kind, int64_t W, void *stream)
@@ -138,8 +94,7 @@ int bisip_move_run_dev(bisip_ctx *c, const bisip_move_args *first, const int32_t
                        int64_t thin_by, void *stream)
 {
     if (!c || !first || !kinds) return fail(BISIP_EINVAL, "null argument");
-    if (thin_by < 1 || n_steps % thin_by) return fail(BISIP_EINVAL, "n_steps=%lld must be a multiple of thin_by=%lld", (long long)n_steps, (long long)thin_by);
-    if (W < 2 || n_steps < 0) return fail(BISIP_EINVAL, "bad W=%lld or n_steps=%lld", (long long)W, (long long)n_steps);
+    if (const int rc = check_chunk(W, n_steps, thin_by)) return rc;
     // W is the total number of walkers (bisip_stretch_run_dev); the moves' refusals speak of one ensemble's
     const int64_t Wp = c->E > 1 ? first->stretch.walkers_per_spectrum : W;
     if (c->E > 1 && (Wp < 2 || (Wp & 1) || Wp * c->E != W))
@@ -155,17 +110,14 @@ int bisip_move_run_dev(bisip_ctx *c, const bisip_move_args *first, const int32_t
     if (!f.coords || !f.logp || !f.status) return fail(BISIP_EINVAL, "null buffer");
     if (stretch && (!f.active || !f.partner || !f.zz || !f.factor || !f.logu)) return fail(BISIP_EINVAL, "null stretch stream");
     HIP_TRY(hipSetDevice(c->device));
-    const int64_t nh = (W + 1) / 2;
+    const ChunkWalk walk(W, c->ndim, n_steps, thin_by, f.chain_row, f.logp_row);
     bisip_move_args u = *first;
     for (int64_t k = 0; k < n_steps; ++k) {
         for (int h = 0; h < 2; ++h) {
-            const int64_t off = (k * 2 + h) * nh;
+            const ChunkWalk::Half half = walk.at(k, h);
+            const int64_t off = half.off;
             bisip_stretch_args &s = u.stretch;
-            s.n_slots = h ? W / 2 : nh;
-            const bool store = ((k + 1) % thin_by) == 0;   // the walkers of BOTH halves of a stored step
-            const int64_t srow = k / thin_by;
-            s.chain_row = (store && f.chain_row) ? f.chain_row + srow * W * c->ndim : nullptr;
-            s.logp_row = (store && f.logp_row) ? f.logp_row + srow * W : nullptr;
+            s.n_slots = half.n_slots; s.chain_row = half.chain_row; s.logp_row = half.logp_row;
             int rc;
             if (kinds[k] == BISIP_MOVE_STRETCH) {
                 s.active = f.active + off; s.partner = f.partner + off;

@@ -1,39 +1,10 @@
 // dispatch_stretch.hip -- stretch-move launches, single spectrum: half-step / eval / apply /
-// persistent (the batch-of-spectra instantiations live in dispatch_stretch_batch.hip).
+// persistent (the batch-of-spectra instantiations live in dispatch_stretch_batch.hip).  The functor a launch takes
+// comes from lp_build.h.
 #include "stretch_launch.h"
 
 using namespace bisip;
 using namespace bisip::host;
-
-namespace {
-
-template <class M>
-int stretch_generic(const bisip_ctx *c, const StretchWork &a, hipStream_t st)
-{
-    const ModelOperands o{c->d_cb_lp ? c->d_cb_lp : c->d_cb, c->N, c->lconst};
-    if constexpr (CoopLimit<M>::value > 0) {      // (else one lane per slot: the other kernels are never instantiated)
-        switch (stretch_lanes(a)) {
-        case 8: { GenericLP<M, 8> lp; lp.o = o; lp.b = c->bounds; return launch_stretch(a, lp, st); }     // (the multi-workgroup sampler only)
-        case 4: { GenericLP<M, 4> lp; lp.o = o; lp.b = c->bounds; return launch_stretch(a, lp, st); }
-        case 2: { GenericLP<M, 2> lp; lp.o = o; lp.b = c->bounds; return launch_stretch(a, lp, st); }
-        default: break;
-        }
-    }
-    GenericLP<M, 1> lp; lp.o = o; lp.b = c->bounds;
-    return launch_stretch(a, lp, st);
-}
-
-template <int P, bool COMP>
-int stretch_reduced(const bisip_ctx *c, const StretchWork &a, hipStream_t st)
-{
-    ReducedLP<P, COMP> lp;
-    fill_reduced<P, COMP>(c, lp.r);
-    lp.lconst = c->lconst;
-    lp.b = c->bounds;
-    return launch_stretch(a, lp, st);
-}
-
-}  // namespace
 
 namespace bisip {
 namespace host {
@@ -63,18 +34,10 @@ int dispatch_stretch(const bisip_ctx *c, const StretchWork &a, long long Wp, hip
         if (Wp < 2 || (Wp & 1)) return fail(BISIP_EINVAL, "batch context: walkers_per_spectrum must be even and >= 2, got %lld", Wp);
         return dispatch_stretch_batch(c, a, Wp, st);
     }
-    if (c->model_id == BISIP_MODEL_POLYDECOMP) {
-        const int v = effective_variant(c);
-        // the sampler kernels exist for the reduced and the collapsed formulation only; running
-        // another one here would store log-probabilities that bisip_logprob does not reproduce
-        // bit for bit, so say so and let the caller drive the move from the host
-        if (v == BISIP_VARIANT_FAITHFUL || v == BISIP_VARIANT_WAVE)
-            return fail(BISIP_EUNSUPPORTED, "the device stretch move has no kernel for the faithful / wave "
-                        "formulation: use variant auto, reduced or collapsed, or the host-loop sampler");
-        if (v == BISIP_VARIANT_REDUCED) return with_pd_degree(c, "stretch", [&](auto p) { return stretch_reduced<p, false>(c, a, st); });
-        if (v == BISIP_VARIANT_REDUCED_COMP) return with_pd_degree(c, "stretch", [&](auto p) { return stretch_reduced<p, true>(c, a, st); });
-    }
-    return with_model(c, "stretch", [&](auto m) { return stretch_generic<typename decltype(m)::type>(c, a, st); });
+    return with_lone_lp<8>(c, stretch_lanes(a), "stretch",      // (eight lanes: the multi-workgroup sampler only)
+                           "the device stretch move has no kernel for the faithful / wave "
+                           "formulation: use variant auto, reduced or collapsed, or the host-loop sampler",
+                           [&](const auto &lp) { return launch_stretch(a, lp, st); });
 }
 
 int dispatch_apply(const bisip_ctx *c, const StretchArgs &a, hipStream_t st)

@@ -1,9 +1,12 @@
 // host.h -- what the translation units of libbisip_hip.so share: the layout of the QR-reduced tiers'
-// operands, the context, the error plumbing and the dispatch entry points.  The kernels are templates, so every dispatch_*.hip
-// instantiates only its own family and the units compile in parallel.
+// operands, the walk over a chunk's half-steps and the draw kernels' launch shape, the context, the error plumbing and
+// the dispatch entry points.  The kernels are templates, so every dispatch_*.hip instantiates only its own family and
+// the units compile in parallel; the log-probability functor a sampler kernel takes is built from a context in one
+// place for all of them (lp_build.h).
 #pragma once
 #include <algorithm>
 #include <cstddef>
+#include <cstdint>
 #include <cstring>
 
 #include "../../include/bisip_hip.h"
@@ -68,6 +71,50 @@ struct ReducedLayout {
     }
 };
 
+// A chunk of n_steps iterations, walked half-step by half-step, as every launch-per-half-step runner walks it
+// (bisip_stretch_run_dev, the sharded runs, bisip_move_run_dev): where half h of iteration k finds its entries of the
+// (n_steps, 2, nh) stream arrays, how many slots it has, and the chain rows it stores to.  Plain C++ as well.
+struct ChunkWalk {
+    int64_t W, ndim, n_steps, thin_by, nh;
+    double *chain_row, *logp_row;     // row 0 of the chunk's stored chain (n_steps / thin_by, W, ndim) and (.., W), or null
+
+    struct Half {
+        int64_t off, n_slots;              // offset into the stream arrays; nh, or W / 2 in the smaller half
+        double *chain_row, *logp_row;      // null unless the iteration is stored (and the chunk has the array)
+    };
+
+    ChunkWalk(int64_t W_, int64_t ndim_, int64_t n_steps_, int64_t thin_by_, double *chain_row_, double *logp_row_)
+        : W(W_), ndim(ndim_), n_steps(n_steps_), thin_by(thin_by_), nh((W_ + 1) / 2), chain_row(chain_row_), logp_row(logp_row_) {}
+
+    Half at(int64_t k, int h) const
+    {
+        const bool store = ((k + 1) % thin_by) == 0;   // the walkers of BOTH halves of a stored step
+        const int64_t srow = k / thin_by;
+        return Half{(k * 2 + h) * nh, h ? W / 2 : nh, (store && chain_row) ? chain_row + srow * W * ndim : nullptr,
+                    (store && logp_row) ? logp_row + srow * W : nullptr};
+    }
+};
+
+// The launch shape of a draw kernel (k_stretch_draw, k_move_draw) over `halves` half-steps of per_half slots each.
+// GRID: x covers the slots of one half-step, (y, z) the half-steps -- the index arithmetic of a flat 64-bit grid was
+// four 64-bit divisions per slot.  FLAT: one 32-bit index over everything (two 32-bit divisions), for ensembles too
+// small to fill a workgroup per half-step.  The other two are refusals (launch_draw has their texts).  halves >= 1.
+struct DrawGrid {
+    enum Shape { FLAT, GRID, TOO_MANY_SLOTS, TOO_MANY_HALVES } shape;
+    unsigned gx, gy, gz;
+};
+
+inline DrawGrid draw_grid(long long per_half, long long halves)
+{
+    if (per_half < 256 && per_half * halves + 256 <= 0xffffffffLL)
+        return DrawGrid{DrawGrid::FLAT, (unsigned)((per_half * halves + 255) / 256), 1u, 1u};
+    if ((per_half + 255) / 256 > 0x7fffffffLL) return DrawGrid{DrawGrid::TOO_MANY_SLOTS, 0u, 0u, 0u};
+    const unsigned gy = (unsigned)(halves < 32768 ? halves : 32768);
+    const long long gz = (halves + gy - 1) / gy;
+    if (gz > 65535) return DrawGrid{DrawGrid::TOO_MANY_HALVES, 0u, 0u, 0u};
+    return DrawGrid{DrawGrid::GRID, (unsigned)((per_half + 255) / 256), gy, (unsigned)gz};
+}
+
 }  // namespace host
 }  // namespace bisip
 
@@ -76,7 +123,6 @@ struct ReducedLayout {
 
 #include <cmath>
 #include <cstdarg>
-#include <cstdint>
 #include <cstdio>
 #include <new>
 #include <type_traits>
@@ -316,6 +362,39 @@ int dispatch_forward(const bisip_ctx *c, const double *theta, int64_t W, double 
                      long long count = 1);
 int dispatch_forward_columns(const bisip_ctx *c, const double *theta, int64_t W, double *cols, hipStream_t st, long long spectrum,
                              long long count, int kind = BISIP_RESPONSE_RI);
+
+// The refusals in front of every walk over a chunk (ChunkWalk).  own_range: the caller states W and the step range
+// itself, in its own words (the Philox entry points, which bound both by the counter's 32-bit words).
+inline int check_chunk(int64_t W, int64_t n_steps, int64_t thin_by, bool own_range = false)
+{
+    if (thin_by < 1 || n_steps % thin_by) return fail(BISIP_EINVAL, "n_steps=%lld must be a multiple of thin_by=%lld", (long long)n_steps, (long long)thin_by);
+    if (!own_range && (W < 2 || n_steps < 0)) return fail(BISIP_EINVAL, "bad W=%lld or n_steps=%lld", (long long)W, (long long)n_steps);
+    return BISIP_OK;
+}
+
+// what every draw kernel's arguments start with (sampler_kernels.h: DrawHead), but for the launch shape
+inline DrawHead draw_head(const bisip_ctx *c, int64_t W, uint64_t seed, int64_t step0, int64_t n_steps, const int32_t *d_perm)
+{
+    DrawHead d;
+    d.W = W; d.nh = (W + 1) / 2; d.n_steps = n_steps; d.step0 = step0; d.E = c->E; d.e0 = c->spectrum_offset;
+    d.flat = 0;
+    d.seed_lo = (unsigned int)(seed & 0xffffffffu); d.seed_hi = (unsigned int)(seed >> 32);
+    d.perm = d_perm;
+    return d;
+}
+
+// one launch of a draw kernel over arguments that begin with a DrawHead `s`, in the shape draw_grid chooses
+template <class Args>
+int launch_draw(long long per_half, long long halves, void (*kernel)(Args), Args d, hipStream_t st)
+{
+    const DrawGrid g = draw_grid(per_half, halves);
+    if (g.shape == DrawGrid::TOO_MANY_SLOTS) return fail(BISIP_EINVAL, "too many slots per half-step");
+    if (g.shape == DrawGrid::TOO_MANY_HALVES) return fail(BISIP_EINVAL, "n_steps=%lld too large for one draw (chunk the run)", halves / 2);
+    d.s.flat = g.shape == DrawGrid::FLAT;
+    hipLaunchKernelGGL(kernel, dim3(g.gx, g.gy, g.gz), dim3(256), 0, st, d);
+    HIP_TRY(hipGetLastError());
+    return BISIP_OK;
+}
 
 // dispatch_stretch.hip
 enum StretchKind { STRETCH_HALF, STRETCH_EVAL, STRETCH_PERSIST, STRETCH_GROUP };

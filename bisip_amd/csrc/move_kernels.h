@@ -131,62 +131,42 @@ __global__ __launch_bounds__(BLK) void k_move_half(const MoveArgs a, const LP lp
 // the stream arrays of purposes 4, 5 and 1: (n_steps, 2, E, nh) as k_stretch_draw lays them out, global walker ids
 // ---------------------------------------------------------------------------------
 struct MoveDrawArgs {
-    long long W, nh, n_steps, step0;  // W = walkers per ensemble
-    long long E, e0;
-    int flat;
+    DrawHead s;
     double g0, sigma;                 // DE: gamma = g0 (1 + sigma n)
-    unsigned int seed_lo, seed_hi;
-    const int *perm;                  // (n_steps, 3): A, Ainv, B
     int *active, *p0, *p1, *p2;
     double *gamma, *logu;
 };
 
 static __global__ __launch_bounds__(256) void k_move_draw(const MoveDrawArgs d)
 {
-    const long long per_half = d.E * d.nh;
-    long long kh, slot;                     // iteration * 2 + half; (ensemble, t): the launch shapes of k_stretch_draw
-    if (d.flat) {
-        const unsigned idx32 = blockIdx.x * 256u + threadIdx.x;
-        const unsigned q = idx32 / (unsigned)per_half;
-        kh = q; slot = idx32 - q * (unsigned)per_half;
-    } else {
-        kh = (long long)blockIdx.y + (long long)gridDim.y * blockIdx.z;
-        slot = (long long)blockIdx.x * 256 + threadIdx.x;
-    }
-    if (kh >= 2 * d.n_steps || slot >= per_half) return;
-    const long long k = kh >> 1;
-    const int h = (int)(kh & 1);
-    long long e, t;
-    if (per_half <= 0xffffffffLL) {
-        const unsigned q = (unsigned)slot / (unsigned)d.nh;
-        e = q; t = (long long)((unsigned)slot - q * (unsigned)d.nh);
-    } else {
-        e = slot / d.nh; t = slot % d.nh;
-    }
-    const long long idx = kh * per_half + slot;
-    const long long Ns = h ? d.W / 2 : (d.W + 1) / 2, Nc = d.W - Ns;
-    if (t >= Ns) {  // padding slot of the smaller half
+    DrawSlot q;
+    const DrawSlotKind kind = draw_decode(d.s, q);
+    if (kind == DRAW_OUTSIDE) return;
+    const long long k = q.k, e = q.e, t = q.t, idx = q.idx, W = d.s.W;
+    const int h = q.h;
+    if (kind == DRAW_PADDING) {
         d.active[idx] = 0; d.p0[idx] = 0; d.p1[idx] = 0; d.p2[idx] = 0; d.gamma[idx] = 0.0; d.logu[idx] = 0.0;
         return;
     }
-    const unsigned step = (unsigned)(d.step0 + k), c2 = (unsigned)h | ((unsigned)(d.e0 + e) << 1);
-    const long long Ainv = d.perm[3 * k + 1], B = d.perm[3 * k + 2];
-    const Philox4 r1 = philox4x32_10((unsigned)t, step, c2, 1u, d.seed_lo, d.seed_hi);
-    const Philox4 r4 = philox4x32_10((unsigned)t, step, c2, 4u, d.seed_lo, d.seed_hi);
-    const Philox4 r5 = philox4x32_10((unsigned)t, step, c2, 5u, d.seed_lo, d.seed_hi);
+    const unsigned step = (unsigned)(d.s.step0 + k), c2 = (unsigned)h | ((unsigned)(d.s.e0 + e) << 1);
+    const long long Ns = h ? W / 2 : (W + 1) / 2, Nc = W - Ns;
+    const long long Ainv = d.s.perm[3 * k + 1], B = d.s.perm[3 * k + 2];
+    const Philox4 r1 = philox4x32_10((unsigned)t, step, c2, 1u, d.s.seed_lo, d.s.seed_hi);
+    const Philox4 r4 = philox4x32_10((unsigned)t, step, c2, 4u, d.s.seed_lo, d.s.seed_hi);
+    const Philox4 r5 = philox4x32_10((unsigned)t, step, c2, 5u, d.s.seed_lo, d.s.seed_hi);
     const long long i0 = (long long)(((unsigned long long)r4.v[0] * (unsigned long long)Nc) >> 32);
     long long i1 = (long long)(((unsigned long long)r4.v[1] * (unsigned long long)(Nc - 1)) >> 32);
     if (i1 >= i0) ++i1;
-    const int base = (int)(e * d.W);
-    d.active[idx] = base + perm_inverse(2 * t + h, d.W, Ainv, B);
-    d.p0[idx] = base + perm_inverse(2 * i0 + (1 - h), d.W, Ainv, B);
-    d.p1[idx] = base + perm_inverse(2 * i1 + (1 - h), d.W, Ainv, B);
+    const int base = (int)(e * W);
+    d.active[idx] = base + perm_inverse(2 * t + h, W, Ainv, B);
+    d.p0[idx] = base + perm_inverse(2 * i0 + (1 - h), W, Ainv, B);
+    d.p1[idx] = base + perm_inverse(2 * i1 + (1 - h), W, Ainv, B);
     int third = 0;                          // a half of two has no third member: the field is 0
     if (Nc >= 3) {
         long long i2 = (long long)(((unsigned long long)r4.v[2] * (unsigned long long)(Nc - 2)) >> 32);
         if (i2 >= (i0 < i1 ? i0 : i1)) ++i2;
         if (i2 >= (i0 < i1 ? i1 : i0)) ++i2;
-        third = base + perm_inverse(2 * i2 + (1 - h), d.W, Ainv, B);
+        third = base + perm_inverse(2 * i2 + (1 - h), W, Ainv, B);
     }
     d.p2[idx] = third;
     const double n = sqrt(-2.0 * log(1.0 - u53(r5.v[0], r5.v[1]))) * cos(6.283185307179586 * u53(r5.v[2], r5.v[3]));

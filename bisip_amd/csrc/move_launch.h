@@ -10,14 +10,14 @@ namespace host {
 // lanes per slot of a move's half-step: the stretch launch's rule for the same number of slots
 inline int move_lanes(const MoveArgs &a) { return stretch_lanes(StretchWork{STRETCH_HALF, &a.s, nullptr}); }
 
-// one half-step launch; workgroups as launch_stretch shapes them (four waves once the launch fills the chip)
+// one half-step launch; workgroups as launch_stretch shapes them (four_wave_workgroups)
 template <class LP>
 int launch_move(const MoveArgs &a, int kind, const LP &lp, hipStream_t st)
 {
     auto go = [&](auto move) {
         constexpr int MOVE = decltype(move)::value;
         const long long lanes = a.s.n_slots * LP::L;
-        if (lanes >= 65536)
+        if (four_wave_workgroups(lanes))
             hipLaunchKernelGGL((k_move_half<LP, MOVE, 256>), dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, a, lp);
         else
             hipLaunchKernelGGL((k_move_half<LP, MOVE, 64>), dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, a, lp);

@@ -602,22 +602,35 @@ __global__ __launch_bounds__(64) void k_stretch_apply(const StretchArgs a)
 // are global (e*W + i), the counter's third word is h | (e << 1) and all ensembles share
 // the step's split.
 // ---------------------------------------------------------------------------------
-struct DrawArgs {
+// what every draw kernel's arguments start with (k_move_draw's too): the ensembles, the steps, the key, the split
+struct DrawHead {
     long long W, nh, n_steps, step0;  // W = walkers per ensemble
     long long E;                      // ensembles (E > 1 requires W even)
     long long e0;                     // index of the context's first spectrum in the whole survey
-    int flat;                         // launch shape, see k_stretch_draw
-    double a, ndim_m1;
+    int flat;                         // launch shape, see draw_decode
     unsigned int seed_lo, seed_hi;
     const int *perm;  // (n_steps, 3): A, Ainv, B
+};
+
+struct DrawArgs {
+    DrawHead s;
+    double a, ndim_m1;
     int *active, *partner;
     double *zz, *factor, *logu;
 };
 
+// one thread's entry of the (n_steps, 2, E, nh) stream arrays: iteration k, half h, ensemble e, slot t, at idx
+struct DrawSlot {
+    long long k, e, t, idx;
+    int h;
+};
+enum DrawSlotKind { DRAW_OUTSIDE, DRAW_PADDING, DRAW_LIVE };   // beyond the arrays; the odd slot of the smaller half; a walker's
+
 // Grid: x covers the E*nh slots of one half-step, (y, z) the 2*n_steps half-steps -- the index
 // arithmetic of a flat 64-bit grid was four 64-bit divisions per slot.  `flat`: one 32-bit index over
 // everything (two 32-bit divisions), for ensembles too small to fill a workgroup per half-step.
-static __global__ __launch_bounds__(256) void k_stretch_draw(const DrawArgs d)
+// (host.h: draw_grid chooses between the two.)
+__device__ __forceinline__ DrawSlotKind draw_decode(const DrawHead &d, DrawSlot &s)
 {
     const long long per_half = d.E * d.nh;
     long long kh, slot;                     // iteration * 2 + half; (ensemble, t)
@@ -629,26 +642,34 @@ static __global__ __launch_bounds__(256) void k_stretch_draw(const DrawArgs d)
         kh = (long long)blockIdx.y + (long long)gridDim.y * blockIdx.z;
         slot = (long long)blockIdx.x * 256 + threadIdx.x;
     }
-    if (kh >= 2 * d.n_steps || slot >= per_half) return;
-    const long long k = kh >> 1;
-    const int h = (int)(kh & 1);
-    long long e, t;
+    if (kh >= 2 * d.n_steps || slot >= per_half) return DRAW_OUTSIDE;
+    s.k = kh >> 1;
+    s.h = (int)(kh & 1);
     if (per_half <= 0xffffffffLL) {
         const unsigned q = (unsigned)slot / (unsigned)d.nh;
-        e = q; t = (long long)((unsigned)slot - q * (unsigned)d.nh);
+        s.e = q; s.t = (long long)((unsigned)slot - q * (unsigned)d.nh);
     } else {
-        e = slot / d.nh; t = slot % d.nh;
+        s.e = slot / d.nh; s.t = slot % d.nh;
     }
-    const long long idx = kh * per_half + slot;
-    const long long Ns = h ? d.W / 2 : (d.W + 1) / 2;
-    if (t >= Ns) {  // padding slot of the smaller half
+    s.idx = kh * per_half + slot;
+    return s.t >= (s.h ? d.W / 2 : (d.W + 1) / 2) ? DRAW_PADDING : DRAW_LIVE;
+}
+
+static __global__ __launch_bounds__(256) void k_stretch_draw(const DrawArgs d)
+{
+    DrawSlot q;
+    const DrawSlotKind kind = draw_decode(d.s, q);
+    if (kind == DRAW_OUTSIDE) return;
+    const long long k = q.k, e = q.e, t = q.t, idx = q.idx, W = d.s.W;
+    const int h = q.h;
+    if (kind == DRAW_PADDING) {
         d.active[idx] = 0; d.partner[idx] = 0; d.zz[idx] = 1.0; d.factor[idx] = 0.0; d.logu[idx] = 0.0;
         return;
     }
-    const SlotDraw s = draw_slot(d.W, d.a, d.ndim_m1, d.seed_lo, d.seed_hi, (unsigned)(d.step0 + k), h,
-                                 (unsigned)(d.e0 + e), t, d.perm[3 * k + 1], d.perm[3 * k + 2]);
-    d.active[idx] = (int)(e * d.W) + s.active;
-    d.partner[idx] = (int)(e * d.W) + s.partner;
+    const SlotDraw s = draw_slot(W, d.a, d.ndim_m1, d.s.seed_lo, d.s.seed_hi, (unsigned)(d.s.step0 + k), h,
+                                 (unsigned)(d.s.e0 + e), t, d.s.perm[3 * k + 1], d.s.perm[3 * k + 2]);
+    d.active[idx] = (int)(e * W) + s.active;
+    d.partner[idx] = (int)(e * W) + s.partner;
     d.zz[idx] = s.z;
     d.factor[idx] = s.factor;
     d.logu[idx] = s.logu;

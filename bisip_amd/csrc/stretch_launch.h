@@ -1,7 +1,7 @@
 // stretch_launch.h -- launch helpers shared by the two stretch-move dispatch units
 // (dispatch_stretch.hip: single spectrum; dispatch_stretch_batch.hip: batch of spectra).
 #pragma once
-#include "host.h"
+#include "lp_build.h"
 
 #include <cstdlib>
 
@@ -85,6 +85,10 @@ int launch_group(const PersistArgs &p0, const LP &lp, hipStream_t st)
     }
 }
 
+// a half-step launch that fills the chip (>= one wave per SIMD) goes out as four-wave workgroups, one
+// per CU; smaller ones as single waves so that they spread over as many CUs as possible
+inline bool four_wave_workgroups(long long lanes) { return lanes >= 65536; }
+
 template <class LP>
 int launch_stretch(const StretchWork &work, const LP &lp, hipStream_t st)
 {
@@ -100,8 +104,6 @@ int launch_stretch(const StretchWork &work, const LP &lp, hipStream_t st)
     if (kind == STRETCH_GROUP) return launch_group(*work.persist, lp, st);
     const StretchArgs &a = *work.half;
     if (kind == STRETCH_HALF) {
-        // a launch that fills the chip (>= one wave per SIMD) goes out as four-wave workgroups, one
-        // per CU; smaller ones as single waves so that they spread over as many CUs as possible
         if (a.packed) {
             // the chunk's state is packed (bisip_stretch_run_dev: a single spectrum, one lane per slot, ndim <= 7)
             if constexpr (LP::L == 1 && LP::NDIM < PACKED_ROW && SingleSpectrum<LP>::value) {
@@ -110,7 +112,7 @@ int launch_stretch(const StretchWork &work, const LP &lp, hipStream_t st)
             } else {
                 return fail(BISIP_EUNSUPPORTED, "internal: a packed state for a kernel that has no packed form");
             }
-        } else if (a.n_slots * LP::L >= 65536) {
+        } else if (four_wave_workgroups(a.n_slots * LP::L)) {
             const unsigned grid = (unsigned)((a.n_slots * LP::L + 255) / 256);
             hipLaunchKernelGGL((k_stretch_half<LP, 256>), dim3(grid), dim3(256), 0, st, a, lp);
         } else {

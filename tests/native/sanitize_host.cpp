@@ -11,7 +11,7 @@
 #include <string>
 #include <vector>
 
-#define BISIP_HOST_LAYOUT_ONLY          // host.h's device-free part: the layout of the QR-reduced tiers' operands
+#define BISIP_HOST_LAYOUT_ONLY          // host.h's device-free part: the QR-reduced tiers' operand layout, the chunk walk, the draw grid
 #include "../../bisip_amd/csrc/host.h"
 #include "../../bisip_amd/csrc/host_precompute.h"
 #include "../../include/bisip_hip.h"
@@ -251,10 +251,75 @@ static void layout(int n)
     }
 }
 
+// The walk over a chunk's half-steps (host.h: ChunkWalk) against a restatement: stream offsets, slot counts, the
+// stored rows -- both halves of every thin_by-th iteration and no other -- each inside the chunk's arrays, and
+// null store pointers from a null base (UBSan flags an offset applied to a null pointer).
+static void chunk_walk(int64_t W, int64_t n_steps, int64_t thin_by, bool stores)
+{
+    const int64_t ndim = 3, nh = (W + 1) / 2, rows = n_steps / thin_by;
+    std::vector<double> chain((size_t)(rows * W * ndim) + 1), logp((size_t)(rows * W) + 1);
+    double *const chain0 = stores ? chain.data() : nullptr, *const logp0 = stores ? logp.data() : nullptr;
+    const bisip::host::ChunkWalk walk(W, ndim, n_steps, thin_by, chain0, logp0);
+    EXPECT(walk.nh == nh && walk.n_steps == n_steps);
+    int64_t slots = 0, stored = 0, next_off = 0;
+    for (int64_t k = 0; k < n_steps; ++k) {
+        bool keep = false;                                   // restated by counting: every thin_by-th iteration
+        for (int64_t j = thin_by; j <= k + 1; j += thin_by) keep = keep || j == k + 1;
+        for (int h = 0; h < 2; ++h) {
+            const bisip::host::ChunkWalk::Half half = walk.at(k, h);
+            EXPECT(half.off == next_off);                    // the stream arrays are (n_steps, 2, nh): nh entries a half
+            next_off += nh;
+            EXPECT(half.n_slots == (h == 0 ? W - W / 2 : W / 2));
+            slots += half.n_slots;
+            if (keep && stores) {
+                EXPECT(half.chain_row == chain0 + stored * W * ndim && half.logp_row == logp0 + stored * W);
+                EXPECT(stored < rows);                       // the row lies inside the arrays
+            } else {
+                EXPECT(half.chain_row == nullptr && half.logp_row == nullptr);
+            }
+        }
+        if (keep) ++stored;
+    }
+    EXPECT(slots == n_steps * W && stored == rows && next_off == 2 * n_steps * nh);
+}
+
+// The draw kernels' launch shape (host.h: draw_grid), 64-bit arithmetic alone: flat exactly when a half-step does
+// not fill a workgroup and one 32-bit index covers everything, a workgroup of slack included; otherwise x covers a half-step's slots, (y, z) the half-steps,
+// within the limits of a grid, or the launch is refused.
+static void draw_grids()
+{
+    const long long MAX_HALVES = 32768LL * 65535;            // what (y, z) can cover
+    const long long per_halfs[] = {1, 17, 255, 256, 257, 1LL << 31};
+    const long long halvess[] = {2, 80, 32768, 65536, 2 * MAX_HALVES, 2 * MAX_HALVES + 2};
+    int largest_refused = 0;
+    for (long long per_half : per_halfs)
+        for (long long halves : halvess) {
+            const bisip::host::DrawGrid g = bisip::host::draw_grid(per_half, halves);
+            const bool flat = per_half < 256 && (unsigned long long)per_half * (unsigned long long)halves + 256 <= 0xffffffffULL;
+            EXPECT((g.shape == bisip::host::DrawGrid::FLAT) == flat);
+            if (flat) {
+                EXPECT((long long)g.gx * 256 >= per_half * halves && ((long long)g.gx - 1) * 256 < per_half * halves);
+                EXPECT(g.gy == 1 && g.gz == 1);
+            } else if (halves > MAX_HALVES) {
+                EXPECT(g.shape == bisip::host::DrawGrid::TOO_MANY_HALVES);
+                if (halves == 2 * MAX_HALVES + 2) ++largest_refused;
+            } else {
+                EXPECT(g.shape == bisip::host::DrawGrid::GRID);
+                EXPECT((long long)g.gx * 256 >= per_half && (long long)g.gx <= 0x7fffffffLL);
+                EXPECT((long long)g.gy * g.gz >= halves && g.gy >= 1 && g.gy <= 32768 && g.gz >= 1 && g.gz <= 65535);
+            }
+        }
+    EXPECT(largest_refused == 5);                            // wherever the shape is not flat: every per_half but 1
+    EXPECT(bisip::host::draw_grid(1LL << 40, 2).shape == bisip::host::DrawGrid::TOO_MANY_SLOTS);
+}
+
 int main(int argc, char **argv)
 {
     if (argc > 1) ingest(argv[1]);
     blocks();
+    for (int64_t W : {2, 3, 33}) for (int64_t n_steps : {0, 1, 6}) for (int64_t thin_by : {1, 2, 3})
+        for (bool stores : {false, true}) if (n_steps % thin_by == 0) chunk_walk(W, n_steps, thin_by, stores);
+    draw_grids();
     for (int n : {2, 7, 8, 12}) layout(n);          // degrees 0, 5, 6, 10
     for (int N : {2, 20}) for (int D : {1, 6, 11}) reduced(N, 2 * N, D);
     for (int N : {1, 2, 20, 33}) for (int S : {1, 7, 40}) for (int D : {1, 6, 11})

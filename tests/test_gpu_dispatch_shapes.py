@@ -1,7 +1,7 @@
 """Every model shape a context can have -- PolynomialDecomposition of degree 0 ... 10, Cole-Cole with 1 ... 5 modes, Dias,
 Shin -- through every host entry point that turns the shape into a kernel's template argument (csrc/host.h: with_model,
-with_pd_degree): log-probability and forward of a single spectrum and of a batch, the stretch move's half-step and
-persistent kernels of both.  A wrong case in a dispatch launches a kernel of another degree without any error, so each
+with_pd_degree; csrc/lp_build.h): log-probability and forward of a single spectrum and of a batch, the stretch move's
+half-step and persistent kernels and the other moves' half-step kernels of both.  A wrong case in a dispatch launches a kernel of another degree without any error, so each
 shape is held to invariants the neighbouring tests state for a few shapes only:
 
   * spectrum e of a batch context returns the bits of a context of that spectrum alone (test_gpu_batch.py);
@@ -24,6 +24,7 @@ pytestmark = pytest.mark.gpu
 
 N_FREQ, WALKERS, STEPS = 8, 16, 6
 SPECTRA = (1, 2)                     # synthetic_columns indices of the batch's two spectra
+MOVES = [('de', 1.0), ('snooker', 1.0), ('stretch', 1.0)]
 
 PD = [('PolynomialDecomposition', dict(poly_deg=p)) for p in range(11)]
 OTHERS = [('PeltonColeCole', dict(n_modes=d)) for d in range(1, 6)] + [('Dias2000', {}), ('Shin2015', {})]
@@ -54,15 +55,16 @@ def _force(ctx, variant, name):
 
 
 def _stored_logp_is_logprob(ctx, ndim, p0, n_ensembles):
-    """The last stored row of log-probabilities against ctx.logprob of the last stored coordinates, both sampler paths."""
+    """The last stored row of log-probabilities against ctx.logprob of the last stored coordinates: both sampler paths of
+    the stretch move, then the differential-evolution and snooker moves' half-steps (halves of eight: enough partners)."""
     from bisip_amd.sampler import DeviceEnsembleSampler
-    for persistent, path in ((True, 'persistent'), (False, 'launch-per-half-step')):
-        s = DeviceEnsembleSampler(WALKERS, ndim, ctx, rng='philox', seed=11, n_ensembles=n_ensembles, persistent=persistent,
-                                  live_dangerously=True)
+    for kw, path in ((dict(persistent=True), 'persistent'), (dict(persistent=False), 'launch-per-half-step'),
+                     (dict(persistent=False, moves=MOVES), 'launch-per-half-step')):
+        s = DeviceEnsembleSampler(WALKERS, ndim, ctx, rng='philox', seed=11, n_ensembles=n_ensembles, live_dangerously=True, **kw)
         s.run_mcmc(p0, STEPS)
         assert s.last_path == path, (s.last_path, path)
         last = np.ascontiguousarray(s.get_chain()[-1].reshape(-1, ndim))
-        assert np.array_equal(ctx.logprob(last), s.get_log_prob()[-1].ravel()), (path, n_ensembles)
+        assert np.array_equal(ctx.logprob(last), s.get_log_prob()[-1].ravel()), (kw, n_ensembles)
 
 
 @pytest.mark.parametrize('model,kw,variant', CASES, ids=_case_id)
